@@ -191,6 +191,71 @@ def test_bench_driver_contract_tp2_cpu():
     assert j["value"] > 0 and j["ms_per_step"] > 0
 
 
+@pytest.mark.timeout(120)
+def test_bench_dump_outputs_cpu(tmp_path):
+    """bench.py --dump-outputs writes the last timed step's logits and
+    greedy token as float .npy files, identical from run to run with the
+    same arguments and different once --steps changes the last step; the
+    result line keeps its fields and --full is accepted."""
+    import json
+    import subprocess
+    import sys as _sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(name, steps, *extra):
+        d = tmp_path / name
+        out = subprocess.run(
+            [_sys.executable, "bench.py", "--gpus", "1", "--device", "cpu",
+             "--steps", str(steps), "--warmup", "1", "--prefill", "8",
+             "--dump-outputs", str(d), *extra],
+            cwd=repo, capture_output=True, text=True, timeout=100)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(line) == 1, out.stdout
+        j = json.loads(line[0])
+        assert j["steps"] == steps and j["ms_per_step"] > 0
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype"):
+            assert key in j
+        assert sorted(os.listdir(d)) == ["logits.npy", "next_token.npy"]
+        return {n: np.load(d / f"{n}.npy") for n in ("logits", "next_token")}
+
+    a, b, c = run("a", 3), run("b", 3, "--full"), run("c", 4)
+    assert a["logits"].dtype == np.float32 and a["logits"].shape == (256,)
+    assert a["next_token"].dtype == np.float64
+    assert np.isfinite(a["logits"]).all()
+    assert int(a["next_token"][0]) == int(a["logits"].argmax())
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
+    # one more step moves the decode one position on: other logits
+    assert not np.array_equal(a["logits"], c["logits"])
+
+
+@pytest.mark.timeout(120)
+def test_bench_uses_built_extension_without_jit_load():
+    """bench.py imports the built extension straight from the tree: torch's
+    JIT load(), which needs to write a lock file into the build directory,
+    must not run when the library is already there."""
+    import subprocess
+    import sys as _sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    from dllama_amd.ops import hip_ops
+    hip_ops()  # make sure it is built (the suite runs after the build)
+    code = (
+        "import os, torch.utils.cpp_extension as ce\n"
+        "def boom(*a, **k): raise AssertionError('JIT load() was called')\n"
+        "ce.load = boom\n"
+        "import bench\n"
+        "bench._use_built_extension()\n"
+        "from dllama_amd.ops import hip_ops\n"
+        "m = hip_ops()\n"
+        "assert os.path.dirname(m.__file__).endswith(os.path.join('ops', '_build'))\n"
+        "print('native', m.__file__)\n")
+    out = subprocess.run([_sys.executable, "-c", code], cwd=repo,
+                         capture_output=True, text=True, timeout=100)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert "native" in out.stdout
+
+
 def _api_tp_worker(rank, world, mp_path, tp_path, port, out_q):
     try:
         os.environ["MASTER_ADDR"] = "127.0.0.1"

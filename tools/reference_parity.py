@@ -21,7 +21,49 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from dllama_amd import model_file as mf
 from dllama_amd import tokenizer as tk
 
-REF_SRC = "/root/reference"
+# checkout of b4rtaz/distributed-llama to build the reference binary from
+REF_SRC = os.environ.get("DLLAMA_REFERENCE_SRC", "")
+
+# the reference's recorded outputs for CASES/CHAT_CASE below, with the
+# sha256 of the exact .m/.t files it consumed (tests replay against these
+# without the reference; `--record` regenerates the file)
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..",
+                      "tests", "golden", "reference_parity.json")
+
+# per-arch vocab picks a trajectory with decisive greedy margins (a near-tie
+# anywhere flips between the reference's int8 path and the f32 oracle); chat
+# needs the filler-free 101 vocab (duplicate '~' embeddings = near-tie runs
+# on long decodes)
+CASES = [{"arch": "llama", "vocab_size": 101},
+         {"arch": "qwen3", "vocab_size": 128},
+         {"arch": "qwen3_moe", "vocab_size": 128}]
+PROMPT, STEPS = "hello world, this is", 48
+CHAT_CASE = {"arch": "llama", "vocab_size": 101, "system": "keep it short",
+             "users": ["hello ab", "more cd"]}
+
+
+def file_sha256(path: str) -> str:
+    import hashlib
+    with open(path, "rb") as f:
+        return hashlib.sha256(f.read()).hexdigest()
+
+
+def record(workdir: str, binary: str) -> dict:
+    """Run the reference on every case and return the golden record."""
+    gold = {"prompt": PROMPT, "steps": STEPS, "generate": [], "chat": None}
+    for case in CASES:
+        model, tok = make_ascii_assets(workdir, **case)
+        gold["generate"].append(dict(
+            case, model_sha256=file_sha256(model),
+            tokenizer_sha256=file_sha256(tok),
+            text=run_reference(binary, model, tok, PROMPT, STEPS)))
+    c = CHAT_CASE
+    model, tok = make_ascii_assets(workdir, vocab_size=c["vocab_size"],
+                                   arch=c["arch"])
+    gold["chat"] = dict(
+        c, model_sha256=file_sha256(model), tokenizer_sha256=file_sha256(tok),
+        turns=run_reference_chat(binary, model, tok, c["system"], c["users"]))
+    return gold
 
 
 def build_reference(workdir: str) -> str:
@@ -32,6 +74,9 @@ def build_reference(workdir: str) -> str:
     if not os.path.isdir(REF_SRC) and os.path.exists(prebuilt):
         return prebuilt
     ref = os.path.join(workdir, "refbuild")
+    if not os.path.exists(ref) and not os.path.isdir(REF_SRC):
+        raise SystemExit("set DLLAMA_REFERENCE_SRC to a checkout of "
+                         "b4rtaz/distributed-llama")
     if not os.path.exists(ref):
         shutil.copytree(REF_SRC, ref)
     binary = os.path.join(ref, "dllama")
@@ -255,10 +300,17 @@ USE_HIP = "--hip" in sys.argv  # greedy-compare the GPU path itself
 
 
 def main():
-    argv = [a for a in sys.argv[1:] if a != "--hip"]
+    argv = [a for a in sys.argv[1:] if a not in ("--hip", "--record")]
     workdir = argv[0] if argv else tempfile.mkdtemp(prefix="parity")
     os.makedirs(workdir, exist_ok=True)
     binary = build_reference(workdir)
+    if "--record" in sys.argv:
+        import json
+        with open(GOLDEN, "w") as f:
+            json.dump(record(workdir, binary), f, indent=1, ensure_ascii=True)
+            f.write("\n")
+        print(f"recorded reference outputs -> {os.path.normpath(GOLDEN)}")
+        return 0
     rc = 0
     for arch in ("llama", "qwen3", "qwen3_moe"):
         # per-arch vocab picks a trajectory with decisive greedy margins
