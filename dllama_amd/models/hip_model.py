@@ -13,9 +13,19 @@ Architecture (MI355X-first):
   - TP sync = on-device Q80 pack -> RCCL all-gather -> merge-add kernel
     (reference SYNC_NODE_SLICES + OP_MERGE_ADD) or plain f32 all-reduce
     (sync_type f32).
+
+Three launch schedules share one set of stages (the `_`-prefixed methods
+under "stages": each kernel call site with its argument plumbing exists
+once): `forward_buffers` (explicit norm_quant per matmul; any batch),
+`_forward_dense_deferred` (B=1 decode, quantization deferred into the
+producers' epilogues) and `_forward_prefill_bf16` (library bf16 GEMMs, an
+A/B baseline). tests/test_launch_trace.py pins the resulting launch
+sequences.
 """
 
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
@@ -47,11 +57,25 @@ class Linear:
 
     @classmethod
     def synthetic(cls, d: int, n: int, device, gen: torch.Generator,
-                  scale: float = 0.02) -> "Linear":
-        qs = torch.randint(0, 256, (d, n // 2), dtype=torch.uint8,
+                  scale: float = 0.02, experts: int | None = None) -> "Linear":
+        lead = () if experts is None else (experts,)
+        qs = torch.randint(0, 256, (*lead, d, n // 2), dtype=torch.uint8,
                            device=device, generator=gen)
-        sc = (torch.rand((d, n // QB), device=device, generator=gen) * scale / 8)
+        sc = (torch.rand((*lead, d, n // QB), device=device, generator=gen)
+              * scale / 8)
         return cls(qs, sc.to(torch.float16))
+
+    @classmethod
+    def cat(cls, *parts: "Linear") -> "Linear":
+        """Fuse along the output rows: one GEMV launch, one pass over x."""
+        return cls(torch.cat([p.qs for p in parts]),
+                   torch.cat([p.scales for p in parts]))
+
+    @classmethod
+    def stack(cls, parts: list) -> "Linear":
+        """Experts along a new leading dimension (grouped GEMV layout)."""
+        return cls(torch.stack([p.qs for p in parts]),
+                   torch.stack([p.scales for p in parts]))
 
 
 class QuantBuf:
@@ -62,6 +86,12 @@ class QuantBuf:
         self.q = torch.zeros(rows, n, dtype=torch.int8, device=device)
         self.s = torch.zeros(rows, n // QB, dtype=torch.float32, device=device)
         self.bs = torch.zeros(rows, n // QB, dtype=torch.float32, device=device)
+
+    def triple(self, rows: int | None = None):
+        """(q, s, bs): the whole buffers, or their first `rows` rows."""
+        if rows is None:
+            return self.q, self.s, self.bs
+        return self.q[:rows], self.s[:rows], self.bs[:rows]
 
 
 def _pow2_batch(b: int) -> int:
@@ -74,7 +104,7 @@ def _pow2_batch(b: int) -> int:
 class HipTransformer:
     def __init__(self, config: ModelConfig, device=None, comm: Comm | None = None,
                  n_batches: int = 32, force_sync: bool = False):
-        self.cfg = config
+        self.cfg = c = config
         self.comm = comm or SingleComm()
         # force_sync: run the full TP sync/gather/concat path at world=1
         # (SingleComm collectives are identity) — lets a 1-GPU box validate
@@ -103,7 +133,55 @@ class HipTransformer:
         self.skip_logits = False  # prefill chunks before the last skip wcls
         self._pf_graphs = {}      # skip_logits -> captured 32-token graph
         self._pf_failed = False
+        # per-model constants
+        self.kv_mul = c.n_heads0 // max(1, c.kv_dim0 // c.head_dim)
+        self.rope_style = 1 if c.rope_type == ROPE_FALCON else 0
+        self.fused_rope = self.rope_style == 0 and not c.is_qwen3
+        self.row_bytes = c.dim + 2 * (c.dim // QB)  # one Q80 wire row
+        self._read_options()
         self._alloc_buffers()
+
+    def _read_options(self):
+        """Every DLLAMA_* option of the model, read once per construction."""
+        env = os.environ
+
+        def flag(name: str, default: str) -> bool:
+            return env.get(name, default) == "1"
+
+        self.attn_splits = int(env.get("DLLAMA_ATTN_SPLITS", "8"))
+        # fused quantize-into-wire sync: validated bit-identical on hardware
+        # (test_sync_quant_pack_matches_two_kernel_path); default on
+        self.fused_sync = flag("DLLAMA_FUSED_SYNC", "1")
+        # adaptive K-split schedule: S=1 fused single-kernel attention below
+        # pos 256 (no combine launch), S=8 to the threshold, S=16 beyond
+        # (tools/attn_kv16_probe: S=16 wins from ~pos 512). The decode graph
+        # is recaptured when pos crosses a boundary. DLLAMA_ADAPTIVE_SPLITS=0
+        # (or an explicit DLLAMA_ATTN_SPLITS) pins S.
+        self.adaptive_thresh = int(env.get("DLLAMA_ADAPTIVE_SPLITS", "512"))
+        if ("DLLAMA_ATTN_SPLITS" in env
+                and "DLLAMA_ADAPTIVE_SPLITS" not in env):
+            self.adaptive_thresh = 0
+        # measured-slower fusions kept for shape experiments (profiles r02):
+        # the 16-wave fused FFN streams worse than the 4-wave GEMV + swiglu
+        # pair, and per-wave gate recompute adds ~8 us to each MoE consumer
+        self.fused_ffn = flag("DLLAMA_FUSED_FFN", "0")
+        self.fused_moe = flag("DLLAMA_FUSED_MOE", "0")
+        # deferred-quant dense decode (EPI_RESID_Q + PRO2); =0 reverts to
+        # explicit norm_quant launches
+        self.use_deferred = flag("DLLAMA_DEFERRED", "1")
+        # bf16 prefill: dense prompt chunks run hipBLASLt GEMMs (torch.mm)
+        # over a bf16 copy of the weights. Measured SLOWER than the
+        # hand-written int8-MFMA GEMM at the 32-token chunk shape (5355 vs
+        # 5651 tok/s prefill) and costs a 2x-weight shadow — off by default,
+        # kept as the library baseline for GEMM tuning A/Bs.
+        self.prefill_bf16 = flag("DLLAMA_PREFILL_BF16", "0")
+        # K-split the deferred down-projections (wo/w2 underfill at 1 wg per
+        # 32 rows when dim <= 4096); merged by add_ssq_q. A/B experiment.
+        self.ksplit_resid = int(env.get("DLLAMA_KSPLIT_RESID", "0"))
+        # f16 KV cache by default: halves the attention HBM stream (measured
+        # 1.45x at 1k ctx, 1.7x at 4k — tools/attn_kv16_probe; maxerr ~2e-5
+        # vs f32). DLLAMA_KV_F32=1 reverts to the reference's f32 layout.
+        self.kv_f32 = flag("DLLAMA_KV_F32", "0")
 
     # ------------------------------------------------------------ weights
 
@@ -129,41 +207,33 @@ class HipTransformer:
         def f32(name, layer=-1):
             return torch.from_numpy(np.array(m.f32(name, layer))).to(dev)
 
+        def w13(l, expert=-1):
+            return Linear.cat(lin("block_matmul_w1", l, c.ff_dim0, c.dim, expert),
+                              lin("block_matmul_w3", l, c.ff_dim0, c.dim, expert))
+
         self.embedding = f32("embedding")
         self.final_norm = f32("final_norm")
         self.wcls = lin("final_matmul_logits", -1, c.vocab0, c.dim)
         for l in range(c.n_layers):
             # fuse Q|K|V (and W1|W3) into single GEMV weights: one launch,
             # one pass over x, full-chip grids even for the small K/V shards
-            q = lin("block_matmul_q", l, c.q_dim0, c.dim)
-            kk = lin("block_matmul_k", l, c.kv_dim0, c.dim)
-            v = lin("block_matmul_v", l, c.kv_dim0, c.dim)
             lw = {
-                "qkv": Linear(torch.cat([q.qs, kk.qs, v.qs]),
-                              torch.cat([q.scales, kk.scales, v.scales])),
+                "qkv": Linear.cat(lin("block_matmul_q", l, c.q_dim0, c.dim),
+                                  lin("block_matmul_k", l, c.kv_dim0, c.dim),
+                                  lin("block_matmul_v", l, c.kv_dim0, c.dim)),
                 "wo": lin("block_matmul_wo", l, c.dim, c.q_dim0),
                 "norm0": f32("block_norm_0", l),
                 "norm1": f32("block_norm_1", l),
             }
             if c.is_moe:
+                experts = range(c.n_experts)
                 lw["gate"] = f32("block_moe_gate", l)
-                w13 = []
-                for e in range(c.n_experts):
-                    w1 = lin("block_matmul_w1", l, c.ff_dim0, c.dim, e)
-                    w3 = lin("block_matmul_w3", l, c.ff_dim0, c.dim, e)
-                    w13.append(Linear(torch.cat([w1.qs, w3.qs]),
-                                      torch.cat([w1.scales, w3.scales])))
-                lw["w13"] = Linear(torch.stack([x.qs for x in w13]),
-                                   torch.stack([x.scales for x in w13]))
-                w2 = [lin("block_matmul_w2", l, c.dim, c.ff_dim0, e)
-                      for e in range(c.n_experts)]
-                lw["w2"] = Linear(torch.stack([x.qs for x in w2]),
-                                  torch.stack([x.scales for x in w2]))
+                lw["w13"] = Linear.stack([w13(l, e) for e in experts])
+                lw["w2"] = Linear.stack(
+                    [lin("block_matmul_w2", l, c.dim, c.ff_dim0, e)
+                     for e in experts])
             else:
-                w1 = lin("block_matmul_w1", l, c.ff_dim0, c.dim)
-                w3 = lin("block_matmul_w3", l, c.ff_dim0, c.dim)
-                lw["w13"] = Linear(torch.cat([w1.qs, w3.qs]),
-                                   torch.cat([w1.scales, w3.scales]))
+                lw["w13"] = w13(l)
                 lw["w2"] = lin("block_matmul_w2", l, c.dim, c.ff_dim0)
             if c.is_qwen3:
                 lw["q_norm"] = f32("block_norm_q", l)
@@ -182,11 +252,13 @@ class HipTransformer:
         c, dev = config, self.device
         gen = torch.Generator(device=dev)
         gen.manual_seed(seed + c.rank)
+        experts = c.n_experts if c.is_moe else None
         self.embedding = torch.randn(c.vocab_size, c.dim, device=dev,
                                      generator=gen) * 0.02
         self.final_norm = torch.ones(c.dim, device=dev)
         self.wcls = Linear.synthetic(c.vocab0, c.dim, dev, gen)
         for l in range(c.n_layers):
+            # the draw order below fixes the weights: keep it
             lw = {
                 "qkv": Linear.synthetic(c.q_dim0 + 2 * c.kv_dim0, c.dim, dev, gen),
                 "wo": Linear.synthetic(c.dim, c.q_dim0, dev, gen),
@@ -196,16 +268,10 @@ class HipTransformer:
             if c.is_moe:
                 lw["gate"] = torch.randn(c.n_experts, c.dim, device=dev,
                                          generator=gen) * 0.02
-                for wn, dd, nn in (("w13", 2 * c.ff_dim0, c.dim),
-                                   ("w2", c.dim, c.ff_dim0)):
-                    qs = torch.randint(0, 256, (c.n_experts, dd, nn // 2),
-                                       dtype=torch.uint8, device=dev, generator=gen)
-                    sc = (torch.rand((c.n_experts, dd, nn // QB), device=dev,
-                                     generator=gen) * 0.02 / 8).to(torch.float16)
-                    lw[wn] = Linear(qs, sc)
-            else:
-                lw["w13"] = Linear.synthetic(2 * c.ff_dim0, c.dim, dev, gen)
-                lw["w2"] = Linear.synthetic(c.dim, c.ff_dim0, dev, gen)
+            lw["w13"] = Linear.synthetic(2 * c.ff_dim0, c.dim, dev, gen,
+                                         experts=experts)
+            lw["w2"] = Linear.synthetic(c.dim, c.ff_dim0, dev, gen,
+                                        experts=experts)
             if c.is_qwen3:
                 lw["q_norm"] = torch.ones(c.head_dim, device=dev)
                 lw["k_norm"] = torch.ones(c.head_dim, device=dev)
@@ -235,42 +301,7 @@ class HipTransformer:
         # (16 slots each on their own cacheline; atomics to one line serialize)
         self.ssq = torch.zeros(2 * c.n_layers + 1, NB, 16 * 32, device=dev)
         self.amax_scratch = torch.zeros(self.amax_blocks, dtype=torch.int64, device=dev)
-        import os as _os
-        self.attn_splits = int(_os.environ.get("DLLAMA_ATTN_SPLITS", "8"))
-        # fused quantize-into-wire sync: validated bit-identical on hardware
-        # (test_sync_quant_pack_matches_two_kernel_path); default on
-        self.fused_sync = _os.environ.get("DLLAMA_FUSED_SYNC", "1") == "1"
-        # adaptive K-split schedule: S=1 fused single-kernel attention below
-        # pos 256 (no combine launch), S=8 to the threshold, S=16 beyond
-        # (tools/attn_kv16_probe: S=16 wins from ~pos 512). The decode graph
-        # is recaptured when pos crosses a boundary. DLLAMA_ADAPTIVE_SPLITS=0
-        # (or an explicit DLLAMA_ATTN_SPLITS) pins S.
-        self.adaptive_thresh = int(_os.environ.get("DLLAMA_ADAPTIVE_SPLITS", "512"))
-        # measured-slower fusions kept for shape experiments (profiles r02):
-        # the 16-wave fused FFN streams worse than the 4-wave GEMV + swiglu
-        # pair, and per-wave gate recompute adds ~8 us to each MoE consumer
-        self.fused_ffn = _os.environ.get("DLLAMA_FUSED_FFN", "0") == "1"
-        self.fused_moe = _os.environ.get("DLLAMA_FUSED_MOE", "0") == "1"
-        # deferred-quant dense decode (EPI_RESID_Q + PRO2); =0 reverts to
-        # explicit norm_quant launches
-        self.use_deferred = _os.environ.get("DLLAMA_DEFERRED", "1") == "1"
-        # bf16 prefill: dense prompt chunks run hipBLASLt GEMMs (torch.mm)
-        # over a bf16 copy of the weights. Measured SLOWER than the
-        # hand-written int8-MFMA GEMM at the 32-token chunk shape (5355 vs
-        # 5651 tok/s prefill) and costs a 2x-weight shadow — off by default,
-        # kept as the library baseline for GEMM tuning A/Bs.
-        self.prefill_bf16 = _os.environ.get("DLLAMA_PREFILL_BF16", "0") == "1"
-        # K-split the deferred down-projections (wo/w2 underfill at 1 wg per
-        # 32 rows when dim <= 4096); merged by add_ssq_q. A/B experiment.
-        self.ksplit_resid = int(_os.environ.get("DLLAMA_KSPLIT_RESID", "0"))
-        if ("DLLAMA_ATTN_SPLITS" in _os.environ
-                and "DLLAMA_ADAPTIVE_SPLITS" not in _os.environ):
-            self.adaptive_thresh = 0
-        # split scratch sized for the current S (the adaptive schedule
-        # reallocates on recapture: 8 short ctx, 16 past 512, 32 past 2k)
-        self.attn_ml = torch.zeros(NB * c.n_heads0 * self.attn_splits * 2, device=dev)
-        self.attn_o = torch.zeros(NB * c.n_heads0 * self.attn_splits * c.head_dim,
-                                  device=dev)
+        self._alloc_attn_scratch()
         self.attn_counter = torch.zeros(NB * c.n_heads0, dtype=torch.int32, device=dev)
         if self.tp_path:
             # per-batch-size contiguous gather buffers: collectives need a
@@ -282,9 +313,9 @@ class HipTransformer:
             self.argmax_scratch_full = torch.zeros(
                 -(-c.world * c.vocab0 // 4096), dtype=torch.int64, device=dev)
             if c.sync_type == Q80:
-                row_bytes = c.dim + 2 * (c.dim // QB)
-                self.sync_out = torch.zeros(NB * row_bytes, dtype=torch.uint8, device=dev)
-                self.sync_in = {n: torch.zeros(c.world, n * row_bytes,
+                self.sync_out = torch.zeros(NB * self.row_bytes,
+                                            dtype=torch.uint8, device=dev)
+                self.sync_in = {n: torch.zeros(c.world, n * self.row_bytes,
                                                dtype=torch.uint8, device=dev)
                                 for n in nbs}
         if c.is_moe:
@@ -295,6 +326,15 @@ class HipTransformer:
             self.moe_out13 = torch.zeros(S, 2 * c.ff_dim0, device=dev)
             self.moe_dq = QuantBuf(S, c.ff_dim0, dev)
             self.moe_y = torch.zeros(S, c.dim, device=dev)
+
+    def _alloc_attn_scratch(self):
+        """Flash-decode split scratch sized for the current S (the adaptive
+        schedule reallocates on recapture: 8 short ctx, 16 past 512, 32
+        past 2k)."""
+        c, dev = self.cfg, self.device
+        n = self.n_batches * c.n_heads0 * self.attn_splits
+        self.attn_ml = torch.zeros(n * 2, device=dev)
+        self.attn_o = torch.zeros(n * c.head_dim, device=dev)
 
     def _dequant_bf16(self, lin: Linear) -> torch.Tensor:
         """Q40 planes -> bf16 weight matrix on device (prefill GEMM shadow;
@@ -329,43 +369,18 @@ class HipTransformer:
         self._build_bf16_shadow()
         cache = R.rope_cache(c.seq_len, c.head_dim, c.rope_theta, c.rope_scaling)
         self.rope_cache = cache.reshape(c.seq_len, c.head_dim).contiguous().to(dev)
-        # f16 KV cache by default: halves the attention HBM stream (measured
-        # 1.45x at 1k ctx, 1.7x at 4k — tools/attn_kv16_probe; maxerr ~2e-5
-        # vs f32). DLLAMA_KV_F32=1 reverts to the reference's f32 layout.
-        import os as _os
-        kv_dt = (torch.float32 if _os.environ.get("DLLAMA_KV_F32") == "1"
-                 else torch.float16)
+        kv_dt = torch.float32 if self.kv_f32 else torch.float16
         self.k_cache = [torch.zeros(c.seq_len, c.kv_dim0, dtype=kv_dt, device=dev)
                         for _ in range(c.n_layers)]
         self.v_cache = [torch.zeros(c.seq_len, c.kv_dim0, dtype=kv_dt, device=dev)
                         for _ in range(c.n_layers)]
-        self.rope_style = 1 if c.rope_type == ROPE_FALCON else 0
 
-    # ------------------------------------------------------------ forward
+    # ------------------------------------------------------------ stages
 
-    def _sync_partial(self, NB: int, slot: int):
-        """TP>1: all-reduce self.partial[:NB] into x (+= sum of partials),
-        accumulating the residual row's sum-of-squares into ssq[slot]."""
-        c = self.cfg
-        if c.sync_type == Q80:
-            nb_dim = c.dim // QB
-            row_bytes = c.dim + 2 * nb_dim
-            out = self.sync_out[: NB * row_bytes]
-            if getattr(self, "fused_sync", False):
-                # quantize straight into the wire buffer, one pass
-                # (default; DLLAMA_FUSED_SYNC=0 splits it)
-                self.k.sync_quant_pack(self.partial[:NB], out)
-            else:
-                q = self.xq  # reuse dim-sized quant buffer
-                self.k.q80_quantize(self.partial[:NB], q.q[:NB], q.s[:NB], q.bs[:NB])
-                self.k.sync_pack(q.q[:NB], q.s[:NB], out)
-            inb = self.sync_in[NB]
-            self.comm.all_gather(inb, out)
-            self.k.merge_add(self.x[:NB], inb.view(c.world, NB, row_bytes),
-                             self.ssq[slot])
-        else:
-            self.comm.allreduce_(self.partial[:NB])
-            self.k.add_ssq(self.x[:NB], self.partial[:NB], self.ssq[slot], NB)
+    def _norm_quant(self, wn, slot: int, NB: int, *out_f32, **kw):
+        """x[:NB] * wn * inv_rms(ssq[slot]) -> Q80 triple in xq."""
+        self.k.norm_quant(self.x[:NB], wn, self.ssq[slot], *self.xq.triple(NB),
+                          NB, self.cfg.norm_eps, *out_f32, **kw)
 
     def _mm(self, lin: Linear, qb: QuantBuf, out, NB: int, amax=None):
         """Batched matmul dispatch: decode batches use the dot4 GEMV,
@@ -374,7 +389,93 @@ class HipTransformer:
             self.k.q40_gemm(lin.qs, lin.scales, qb.q, qb.s, out, NB,
                             self.gemm_part)
         else:
-            self.k.q40_gemv(lin.qs, lin.scales, qb.q, qb.s, qb.bs, out, NB, amax)
+            self.k.q40_gemv(lin.qs, lin.scales, *qb.triple(), out, NB, amax)
+
+    def _norm_mm(self, lin: Linear, wn, slot: int, out, NB: int, amax=None):
+        """Normed + quantized x -> matmul. (A norm+quant GEMV prologue was
+        measured VALU-bound, 2x slower on the big GEMVs: x is re-quantized
+        per workgroup.)"""
+        self._norm_quant(wn, slot, NB)
+        self._mm(lin, self.xq, out, NB, amax)
+
+    def _gemv_rope(self, l: int, lw: dict, NB: int, **deferred):
+        """QKV GEMV with llama rope + KV write in its epilogue."""
+        c = self.cfg
+        self.k.q40_gemv_rope(lw["qkv"].qs, lw["qkv"].scales, *self.xq.triple(),
+                             self.qkv_out, NB, self.rope_cache, self.pos,
+                             self.k_cache[l], self.v_cache[l], c.q_dim0,
+                             c.kv_dim0, c.head_dim, **deferred)
+
+    def _qknorm_rope_kv(self, l: int, lw: dict, B: int):
+        """Per-head q/k rmsnorm (qwen3), rope and KV write on qkv_out, for
+        the schedules whose QKV matmul has no rope epilogue."""
+        c, k = self.cfg, self.k
+        if c.is_qwen3 and self.rope_style == 1:
+            # one launch (replaces 2x rmsnorm_rows_s + rope_kv = ~9 us/layer
+            # of launch overhead in the captured graph)
+            k.rope_kv_qknorm(self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0,
+                             self.rope_cache, self.pos, self.k_cache[l],
+                             self.v_cache[l], c.head_dim, lw["q_norm"],
+                             lw["k_norm"], c.norm_eps, B)
+            return
+        if c.is_qwen3:
+            for col0, width, wn in ((0, c.q_dim0, lw["q_norm"]),
+                                    (c.q_dim0, c.kv_dim0, lw["k_norm"])):
+                k.rmsnorm_rows_s(self.qkv_out, self.qkv_ld, col0,
+                                 width // c.head_dim, B, wn, c.head_dim,
+                                 c.norm_eps)
+        k.rope_kv(self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0,
+                  self.rope_cache, self.pos, self.k_cache[l], self.v_cache[l],
+                  c.head_dim, self.rope_style, B)
+
+    def _attn(self, l: int, B: int, emit_q80: bool = True):
+        """Attention over layer l's cache into zbuf[:B]; emit_q80 also
+        writes the Q80 triple zq that the wo matmul consumes."""
+        c = self.cfg
+        self.k.attn(self.qkv_out, self.qkv_ld, self.k_cache[l], self.v_cache[l],
+                    self.zbuf[:B], self.pos, B, c.n_heads0, self.kv_mul,
+                    c.head_dim, self.attn_splits, self.attn_ml, self.attn_o,
+                    self.attn_counter, *(self.zq.triple() if emit_q80 else ()))
+
+    def _swiglu_q80(self, out13, rows: int, qb: QuantBuf, *act):
+        """act(w1 x) * (w3 x) over the fused W1|W3 output -> Q80 triple."""
+        f = self.cfg.ff_dim0
+        self.k.swiglu_q80(out13, out13[:, f:], 2 * f, f, rows,
+                          *qb.triple(rows), *act)
+
+    def _wire_exchange(self, n: int, ssq_slot, wnorm=None):
+        """Q80 wire sync, given this rank's n packed rows in sync_out:
+        all-gather, then merge-add every rank's slice into x[:n] with the
+        row sum-of-squares into ssq_slot. With wnorm the merge also emits
+        the next matmul's deferred quant into xq."""
+        c = self.cfg
+        inb = self.sync_in[n]
+        self.comm.all_gather(inb, self.sync_out[: n * self.row_bytes])
+        wire = inb.view(c.world, n, self.row_bytes)
+        if wnorm is None:
+            self.k.merge_add(self.x[:n], wire, ssq_slot)
+        else:
+            self.k.merge_add_q(self.x[:n], wire, ssq_slot, wnorm,
+                               *self.xq.triple())
+
+    def _sync_partial(self, NB: int, slot: int):
+        """TP>1: all-reduce self.partial[:NB] into x (+= sum of partials),
+        accumulating the residual row's sum-of-squares into ssq[slot]."""
+        k = self.k
+        if self.cfg.sync_type != Q80:
+            self.comm.allreduce_(self.partial[:NB])
+            k.add_ssq(self.x[:NB], self.partial[:NB], self.ssq[slot], NB)
+            return
+        out = self.sync_out[: NB * self.row_bytes]
+        if self.fused_sync:
+            # quantize straight into the wire buffer, one pass
+            # (default; DLLAMA_FUSED_SYNC=0 splits it)
+            k.sync_quant_pack(self.partial[:NB], out)
+        else:
+            q, s, bs = self.xq.triple(NB)  # reuse dim-sized quant buffer
+            k.q80_quantize(self.partial[:NB], q, s, bs)
+            k.sync_pack(q, s, out)
+        self._wire_exchange(NB, self.ssq[slot])
 
     def _proj_merge(self, lin: Linear, qb: QuantBuf, slot: int, NB: int):
         """Down-projection + residual fold: TP=1 decode fuses the add + ssq
@@ -382,7 +483,7 @@ class HipTransformer:
         earlier +6.5us was atomics serializing on one cacheline)."""
         k = self.k
         if not self.tp_path and NB < 8:
-            k.q40_gemv_resid(lin.qs, lin.scales, qb.q, qb.s, qb.bs,
+            k.q40_gemv_resid(lin.qs, lin.scales, *qb.triple(),
                              self.x, self.ssq[slot], NB)
             return
         self._mm(lin, qb, self.partial, NB)
@@ -390,6 +491,58 @@ class HipTransformer:
             k.add_ssq(self.x[:NB], self.partial[:NB], self.ssq[slot], NB)
         else:
             self._sync_partial(NB, slot)
+
+    def _proj_merge_deferred(self, lin: Linear, qb: QuantBuf, slot: int, wnorm):
+        """B=1 down-projection + residual fold into x and ssq[slot], which
+        also emits x*wnorm as the next matmul's deferred Q80 input in xq.
+        TP: the GEMV epilogue packs the Q80 wire instead and the merge-add
+        after the all-gather folds the residual and emits the quant
+        (reference SYNC_NODE_SLICES + OP_MERGE_ADD, one fewer launch on
+        each side of the collective)."""
+        k, ssq = self.k, self.ssq[slot]
+        if self.tp_path:
+            k.q40_gemv_pack(lin.qs, lin.scales, *qb.triple(),
+                            self.sync_out[: self.row_bytes])
+            self._wire_exchange(1, ssq, wnorm)
+        elif self.ksplit_resid:
+            k.q40_gemv_ksplit(lin.qs, lin.scales, *qb.triple(),
+                              self.gemm_part, self.ksplit_resid)
+            k.add_ssq_q(self.x[:1], self.gemm_part, ssq, wnorm,
+                        *self.xq.triple(1), self.ksplit_resid)
+        else:
+            k.q40_gemv_resid_q(lin.qs, lin.scales, *qb.triple(), self.x, ssq,
+                               wnorm, *self.xq.triple())
+
+    def _logits(self, B: int, NB: int, slot: int, deferred: bool = False):
+        """wcls matmul over the final norm, TP gather of the vocab shards,
+        and (greedy_feedback, B=1) the on-device argmax into tokens[0]."""
+        c, k = self.cfg, self.k
+        greedy = self.greedy_feedback and B == 1
+        use_amax = greedy and not self.tp_path
+        amax = self.amax_scratch if use_amax else None
+        if deferred:
+            k.q40_gemv(self.wcls.qs, self.wcls.scales, *self.xq.triple(),
+                       self.logits0, 1, amax, ssq_in=self.ssq[slot],
+                       eps=c.norm_eps)
+        else:
+            self._norm_mm(self.wcls, self.final_norm, slot, self.logits0, NB,
+                          amax)
+        if self.tp_path:
+            self.comm.all_gather(self.logits_gather[NB], self.logits0[:NB])
+        if not greedy:
+            return
+        # on-device greedy sampling feeding the next decode step (used by
+        # the fully graph-captured bench loop; real serving samples on host)
+        if use_amax:
+            k.token_from_argmax(self.tokens, self.amax_scratch, self.amax_blocks)
+        else:
+            # TP: gathered slices are contiguous in global vocab order
+            # (row-split wcls), so the flat gather buffer IS the full
+            # logits row; two-kernel argmax, no ATen in the graph
+            k.argmax_token(self.tokens, self.logits_gather[1].view(-1),
+                           self.argmax_scratch_full)
+
+    # ------------------------------------------------------------ forward
 
     def forward_buffers(self, B: int):
         """Run one step over tokens[:B] at positions pos..pos+B-1, writing
@@ -402,121 +555,48 @@ class HipTransformer:
         if (B == 1 and c.dim % 32 == 0 and tp_def_ok
                 and (not c.is_moe
                      or (c.dim % 256 == 0 and c.n_active_experts <= 16))
-                and getattr(self, "use_deferred", True)
-                and not getattr(self, "use_fused_norm", False)):
+                and self.use_deferred):
             return self._forward_dense_deferred()
-        if B >= 8 and getattr(self, "prefill_bf16", False):
+        if B >= 8 and self.prefill_bf16:
             return self._forward_prefill_bf16(B)
-        x = self.x
         self.ssq.zero_()
-        k.embed_gather(self.embedding, self.tokens, x, NB, self.ssq[0])
-
-        kv_mul = c.n_heads0 // max(1, c.kv_dim0 // c.head_dim)
-        fused_rope = self.rope_style == 0 and not c.is_qwen3
-        # Fusing norm+quant into the GEMV prologue re-quantizes x per
-        # workgroup: measured VALU-bound (2x slower on the big GEMVs).
-        # Kept behind a flag for shapes where it might win; off by default.
-        fused_norm = getattr(self, "use_fused_norm", False) and NB <= 4
+        k.embed_gather(self.embedding, self.tokens, self.x, NB, self.ssq[0])
         slot = 0
-
-        def norm_gemv(lin, wn, slot, out, amax=None):
-            """normed+quantized x -> matmul (fused prologue for decode)."""
-            if fused_norm:
-                k.q40_gemv_nq(lin.qs, lin.scales, x, wn, self.ssq[slot],
-                              c.norm_eps, out, NB, amax)
-            else:
-                k.norm_quant(x[:NB], wn, self.ssq[slot], self.xq.q[:NB],
-                             self.xq.s[:NB], self.xq.bs[:NB], NB, c.norm_eps)
-                self._mm(lin, self.xq, out, NB, amax)
-
         for l, lw in enumerate(self.layers):
             # attention block
-            if fused_rope and fused_norm:
-                k.q40_gemv_nq_rope(lw["qkv"].qs, lw["qkv"].scales, x,
-                                   lw["norm0"], self.ssq[slot], c.norm_eps,
-                                   self.qkv_out, NB, self.rope_cache, self.pos,
-                                   self.k_cache[l], self.v_cache[l],
-                                   c.q_dim0, c.kv_dim0, c.head_dim)
-            elif fused_rope and NB < 8:
-                k.norm_quant(x[:NB], lw["norm0"], self.ssq[slot], self.xq.q[:NB],
-                             self.xq.s[:NB], self.xq.bs[:NB], NB, c.norm_eps)
-                k.q40_gemv_rope(lw["qkv"].qs, lw["qkv"].scales, self.xq.q,
-                                self.xq.s, self.xq.bs, self.qkv_out, NB,
-                                self.rope_cache, self.pos, self.k_cache[l],
-                                self.v_cache[l], c.q_dim0, c.kv_dim0, c.head_dim)
-            elif c.is_qwen3 and self.rope_style == 1:
-                # per-head q/k rmsnorm + neox rope + KV write, one launch
-                # (replaces 2x rmsnorm_rows_s + rope_kv = ~9 us/layer of
-                # launch overhead in the captured graph)
-                norm_gemv(lw["qkv"], lw["norm0"], slot, self.qkv_out)
-                k.rope_kv_qknorm(self.qkv_out, self.qkv_ld, c.q_dim0,
-                                 c.kv_dim0, self.rope_cache, self.pos,
-                                 self.k_cache[l], self.v_cache[l], c.head_dim,
-                                 lw["q_norm"], lw["k_norm"], c.norm_eps, B)
+            if self.fused_rope and NB < 8:
+                self._norm_quant(lw["norm0"], slot, NB)
+                self._gemv_rope(l, lw, NB)
             else:
-                norm_gemv(lw["qkv"], lw["norm0"], slot, self.qkv_out)
-                if c.is_qwen3:
-                    k.rmsnorm_rows_s(self.qkv_out, self.qkv_ld, 0,
-                                     c.q_dim0 // c.head_dim, B, lw["q_norm"],
-                                     c.head_dim, c.norm_eps)
-                    k.rmsnorm_rows_s(self.qkv_out, self.qkv_ld, c.q_dim0,
-                                     c.kv_dim0 // c.head_dim, B, lw["k_norm"],
-                                     c.head_dim, c.norm_eps)
-                k.rope_kv(self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0,
-                          self.rope_cache, self.pos, self.k_cache[l],
-                          self.v_cache[l], c.head_dim, self.rope_style, B)
-            k.attn(self.qkv_out, self.qkv_ld, self.k_cache[l], self.v_cache[l],
-                   self.zbuf[:B], self.pos, B, c.n_heads0, kv_mul, c.head_dim,
-                   self.attn_splits, self.attn_ml, self.attn_o,
-                   self.attn_counter, self.zq.q, self.zq.s, self.zq.bs)
+                self._norm_mm(lw["qkv"], lw["norm0"], slot, self.qkv_out, NB)
+                self._qknorm_rope_kv(l, lw, B)
+            self._attn(l, B)
             self._proj_merge(lw["wo"], self.zq, slot + 1, NB)
             slot += 1
 
             # ffn block
             if c.is_moe:
                 # norm once: Q80 triple for the expert GEMVs + f32 for router
-                k.norm_quant(x[:NB], lw["norm1"], self.ssq[slot], self.xq.q[:NB],
-                             self.xq.s[:NB], self.xq.bs[:NB], NB, c.norm_eps,
-                             self.t_norm[:NB])
+                self._norm_quant(lw["norm1"], slot, NB, self.t_norm[:NB])
                 self._moe_ffn(B, NB, lw, slot + 1)
             else:
                 gelu = c.hidden_act == HIDDEN_ACT_GELU
-                if (NB == 1 and not fused_norm and c.ff_dim0 % 32 == 0
-                        and getattr(self, "fused_ffn", False)):
+                if NB == 1 and c.ff_dim0 % 32 == 0 and self.fused_ffn:
                     # fused W1|W3 GEMV + SwiGLU + Q80 emit (one launch
                     # replacing gemv + swiglu_q80)
-                    k.norm_quant(x[:NB], lw["norm1"], self.ssq[slot],
-                                 self.xq.q[:NB], self.xq.s[:NB],
-                                 self.xq.bs[:NB], NB, c.norm_eps)
+                    self._norm_quant(lw["norm1"], slot, NB)
                     k.q40_gemv_swiglu(lw["w13"].qs, lw["w13"].scales,
-                                      self.xq.q, self.xq.s, self.xq.bs,
-                                      self.dq.q, self.dq.s, self.dq.bs, gelu)
+                                      *self.xq.triple(), *self.dq.triple(),
+                                      gelu)
                 else:
-                    norm_gemv(lw["w13"], lw["norm1"], slot, self.ff_out)
-                    k.swiglu_q80(self.ff_out, self.ff_out[:, c.ff_dim0:],
-                                 2 * c.ff_dim0, c.ff_dim0, NB, self.dq.q[:NB],
-                                 self.dq.s[:NB], self.dq.bs[:NB], gelu)
+                    self._norm_mm(lw["w13"], lw["norm1"], slot, self.ff_out, NB)
+                    self._swiglu_q80(self.ff_out, NB, self.dq, gelu)
                 self._proj_merge(lw["w2"], self.dq, slot + 1, NB)
             slot += 1
 
         if self.skip_logits and B > 1:
             return
-        use_amax = (self.greedy_feedback and B == 1 and not self.tp_path)
-        norm_gemv(self.wcls, self.final_norm, slot, self.logits0,
-                  self.amax_scratch if use_amax else None)
-        if self.tp_path:
-            self.comm.all_gather(self.logits_gather[NB], self.logits0[:NB])
-        if self.greedy_feedback and B == 1:
-            # on-device greedy sampling feeding the next decode step (used by
-            # the fully graph-captured bench loop; real serving samples on host)
-            if use_amax:
-                k.token_from_argmax(self.tokens, self.amax_scratch, self.amax_blocks)
-            else:
-                # TP: gathered slices are contiguous in global vocab order
-                # (row-split wcls), so the flat gather buffer IS the full
-                # logits row; two-kernel argmax, no ATen in the graph
-                k.argmax_token(self.tokens, self.logits_gather[1].view(-1),
-                               self.argmax_scratch_full)
+        self._logits(B, NB, slot)
 
     def _forward_prefill_bf16(self, B: int):
         """Dense prompt chunks as hipBLASLt bf16 GEMMs over the weight
@@ -531,43 +611,24 @@ class HipTransformer:
         c, k = self.cfg, self.k
         NB = _pow2_batch(B)
         x = self.x
-        eps = c.norm_eps
+
+        def norm_mm(wn, slot, w_bf16):
+            k.norm_f32(x[:NB], wn, self.ssq[slot], self.t_norm[:NB], NB,
+                       c.norm_eps)
+            return torch.mm(self.t_norm[:NB].bfloat16(), w_bf16.t())
+
         self.ssq.zero_()
         k.embed_gather(self.embedding, self.tokens, x, NB, self.ssq[0])
-        kv_mul = c.n_heads0 // max(1, c.kv_dim0 // c.head_dim)
         slot = 0
         for l, lw in enumerate(self.layers):
-            k.norm_f32(x[:NB], lw["norm0"], self.ssq[slot], self.t_norm[:NB],
-                       NB, eps)
-            self.qkv_out[:NB].copy_(
-                torch.mm(self.t_norm[:NB].bfloat16(), lw["qkv_bf16"].t()))
-            if c.is_qwen3 and self.rope_style == 1:
-                k.rope_kv_qknorm(self.qkv_out, self.qkv_ld, c.q_dim0,
-                                 c.kv_dim0, self.rope_cache, self.pos,
-                                 self.k_cache[l], self.v_cache[l], c.head_dim,
-                                 lw["q_norm"], lw["k_norm"], eps, B)
-            else:
-                if c.is_qwen3:
-                    k.rmsnorm_rows_s(self.qkv_out, self.qkv_ld, 0,
-                                     c.q_dim0 // c.head_dim, B, lw["q_norm"],
-                                     c.head_dim, eps)
-                    k.rmsnorm_rows_s(self.qkv_out, self.qkv_ld, c.q_dim0,
-                                     c.kv_dim0 // c.head_dim, B, lw["k_norm"],
-                                     c.head_dim, eps)
-                k.rope_kv(self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0,
-                          self.rope_cache, self.pos, self.k_cache[l],
-                          self.v_cache[l], c.head_dim, self.rope_style, B)
-            k.attn(self.qkv_out, self.qkv_ld, self.k_cache[l], self.v_cache[l],
-                   self.zbuf[:B], self.pos, B, c.n_heads0, kv_mul, c.head_dim,
-                   self.attn_splits, self.attn_ml, self.attn_o,
-                   self.attn_counter)
+            self.qkv_out[:NB].copy_(norm_mm(lw["norm0"], slot, lw["qkv_bf16"]))
+            self._qknorm_rope_kv(l, lw, B)
+            self._attn(l, B, emit_q80=False)
             partial = torch.mm(self.zbuf[:NB].bfloat16(),
                                lw["wo_bf16"].t()).float()
             k.add_ssq(x[:NB], partial, self.ssq[slot + 1], NB)
             slot += 1
-            k.norm_f32(x[:NB], lw["norm1"], self.ssq[slot], self.t_norm[:NB],
-                       NB, eps)
-            ff = torch.mm(self.t_norm[:NB].bfloat16(), lw["w13_bf16"].t()).float()
+            ff = norm_mm(lw["norm1"], slot, lw["w13_bf16"]).float()
             a, g = ff[:, :c.ff_dim0], ff[:, c.ff_dim0:]
             if c.hidden_act == HIDDEN_ACT_GELU:
                 d = F.gelu(a, approximate="tanh") * g
@@ -578,13 +639,10 @@ class HipTransformer:
             slot += 1
         if self.skip_logits and B > 1:
             return
-        k.norm_f32(x[:NB], self.final_norm, self.ssq[slot], self.t_norm[:NB],
-                   NB, eps)
-        self.logits0[:NB].copy_(
-            torch.mm(self.t_norm[:NB].bfloat16(), self.wcls_bf16.t()))
+        self.logits0[:NB].copy_(norm_mm(self.final_norm, slot, self.wcls_bf16))
 
     def _forward_dense_deferred(self):
-        """B=1 dense decode with DEFERRED activation quantization: the
+        """B=1 decode with DEFERRED activation quantization: the
         down-projection GEMVs emit the next matmul's Q80 input in their own
         epilogue (x*w_norm quantized per wg-local block, scale excluding
         inv_rms), and every consumer GEMV applies inv = rsqrt(ssq/n + eps)
@@ -594,164 +652,67 @@ class HipTransformer:
         merge_add/inv_rms/rms_norm/cast as 4 ops per half-layer,
         llm.cpp:263-270)."""
         c, k = self.cfg, self.k
-        x = self.x
         eps = c.norm_eps
         self.ssq.zero_()
-        k.embed_gather(self.embedding, self.tokens, x, 1, self.ssq[0])
-        kv_mul = c.n_heads0 // max(1, c.kv_dim0 // c.head_dim)
-        fused_rope = self.rope_style == 0 and not c.is_qwen3
+        k.embed_gather(self.embedding, self.tokens, self.x, 1, self.ssq[0])
         # layer 0's norm0 quant comes from a deferred norm_quant (later
         # layers get it from the previous w2's EPI_RESID_Q epilogue)
-        k.norm_quant(x[:1], self.layers[0]["norm0"], self.ssq[0],
-                     self.xq.q[:1], self.xq.s[:1], self.xq.bs[:1], 1, eps,
-                     deferred=True)
+        self._norm_quant(self.layers[0]["norm0"], 0, 1, deferred=True)
         slot = 0
         last = len(self.layers) - 1
         for l, lw in enumerate(self.layers):
             sin = self.ssq[slot]
-            if fused_rope:
-                k.q40_gemv_rope(lw["qkv"].qs, lw["qkv"].scales, self.xq.q,
-                                self.xq.s, self.xq.bs, self.qkv_out, 1,
-                                self.rope_cache, self.pos, self.k_cache[l],
-                                self.v_cache[l], c.q_dim0, c.kv_dim0,
-                                c.head_dim, ssq_in=sin, eps=eps)
+            if self.fused_rope:
+                self._gemv_rope(l, lw, 1, ssq_in=sin, eps=eps)
             else:
-                k.q40_gemv(lw["qkv"].qs, lw["qkv"].scales, self.xq.q,
-                           self.xq.s, self.xq.bs, self.qkv_out, 1,
-                           ssq_in=sin, eps=eps)
-                if c.is_qwen3 and self.rope_style == 1:
-                    k.rope_kv_qknorm(self.qkv_out, self.qkv_ld, c.q_dim0,
-                                     c.kv_dim0, self.rope_cache, self.pos,
-                                     self.k_cache[l], self.v_cache[l],
-                                     c.head_dim, lw["q_norm"], lw["k_norm"],
-                                     eps, 1)
-                else:
-                    if c.is_qwen3:
-                        k.rmsnorm_rows_s(self.qkv_out, self.qkv_ld, 0,
-                                         c.q_dim0 // c.head_dim, 1,
-                                         lw["q_norm"], c.head_dim, eps)
-                        k.rmsnorm_rows_s(self.qkv_out, self.qkv_ld, c.q_dim0,
-                                         c.kv_dim0 // c.head_dim, 1,
-                                         lw["k_norm"], c.head_dim, eps)
-                    k.rope_kv(self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0,
-                              self.rope_cache, self.pos, self.k_cache[l],
-                              self.v_cache[l], c.head_dim, self.rope_style, 1)
-            k.attn(self.qkv_out, self.qkv_ld, self.k_cache[l], self.v_cache[l],
-                   self.zbuf[:1], self.pos, 1, c.n_heads0, kv_mul, c.head_dim,
-                   self.attn_splits, self.attn_ml, self.attn_o,
-                   self.attn_counter, self.zq.q, self.zq.s, self.zq.bs)
+                k.q40_gemv(lw["qkv"].qs, lw["qkv"].scales, *self.xq.triple(),
+                           self.qkv_out, 1, ssq_in=sin, eps=eps)
+                self._qknorm_rope_kv(l, lw, 1)
+            self._attn(l, 1)
             # wo: residual fold + deferred Q80 emit of x*norm1 for the FFN
-            # (TP: the epilogue packs the Q80 wire instead; merge-add after
-            # the all-gather folds the residual and emits the deferred quant
-            # — reference SYNC_NODE_SLICES + OP_MERGE_ADD, one fewer launch
-            # on each side of the collective)
-            if self.tp_path:
-                self._tp_proj_deferred(lw["wo"], self.zq, self.ssq[slot + 1],
-                                       lw["norm1"])
-            elif self.ksplit_resid:
-                k.q40_gemv_ksplit(lw["wo"].qs, lw["wo"].scales, self.zq.q,
-                                  self.zq.s, self.zq.bs, self.gemm_part,
-                                  self.ksplit_resid)
-                k.add_ssq_q(x[:1], self.gemm_part, self.ssq[slot + 1],
-                            lw["norm1"], self.xq.q[:1], self.xq.s[:1],
-                            self.xq.bs[:1], self.ksplit_resid)
-            else:
-                k.q40_gemv_resid_q(lw["wo"].qs, lw["wo"].scales, self.zq.q,
-                                   self.zq.s, self.zq.bs, x,
-                                   self.ssq[slot + 1], lw["norm1"],
-                                   self.xq.q, self.xq.s, self.xq.bs)
+            self._proj_merge_deferred(lw["wo"], self.zq, slot + 1, lw["norm1"])
             slot += 1
+            # the FFN's fold emits the NEXT layer's norm0 quant (final_norm
+            # for logits after the last layer)
             wn = self.final_norm if l == last else self.layers[l + 1]["norm0"]
             if c.is_moe:
-                # MoE deferred FFN: router reads x*norm1*inv directly (no
-                # t_norm buffer), grouped w13 consumes the deferred xq, and
-                # the scale-merge epilogue emits the NEXT layer's deferred
-                # quant — both per-layer norm_quant launches gone here too
-                ka = c.n_active_experts
-                k.router_gemv_norm(lw["gate"], x, lw["norm1"],
-                                   self.ssq[slot], eps, self.moe_router, 1)
-                k.moe_gate(self.moe_router[:1], self.moe_idx, self.moe_wts,
-                           1, ka)
-                k.q40_gemv_grouped(lw["w13"].qs, lw["w13"].scales, self.xq.q,
-                                   self.xq.s, self.xq.bs, self.moe_idx[:ka],
-                                   self.moe_out13, ka,
-                                   ssq_in=self.ssq[slot], eps=eps)
-                k.swiglu_q80(self.moe_out13, self.moe_out13[:, c.ff_dim0:],
-                             2 * c.ff_dim0, c.ff_dim0, ka, self.moe_dq.q[:ka],
-                             self.moe_dq.s[:ka], self.moe_dq.bs[:ka])
-                k.q40_gemv_grouped(lw["w2"].qs, lw["w2"].scales, self.moe_dq.q,
-                                   self.moe_dq.s, self.moe_dq.bs,
-                                   self.moe_idx[:ka], self.moe_y, 1)
-                if self.tp_path:
-                    # expert-weighted sum packed straight into the Q80 wire;
-                    # merge-add after the gather folds residual + emits the
-                    # next deferred quant
-                    rb = c.dim + 2 * (c.dim // QB)
-                    k.scale_merge_pack(self.moe_y, self.moe_wts,
-                                       self.sync_out[:rb], 1, ka, c.dim)
-                    inb = self.sync_in[1]
-                    self.comm.all_gather(inb, self.sync_out[:rb])
-                    k.merge_add_q(x[:1], inb.view(c.world, 1, rb),
-                                  self.ssq[slot + 1], wn, self.xq.q,
-                                  self.xq.s, self.xq.bs)
-                else:
-                    k.scale_merge_add_q(x[:1], self.moe_y, self.moe_wts,
-                                        self.ssq[slot + 1], wn, self.xq.q,
-                                        self.xq.s, self.xq.bs, 1, ka)
+                self._moe_ffn_deferred(lw, slot, wn)
             else:
-                k.q40_gemv(lw["w13"].qs, lw["w13"].scales, self.xq.q,
-                           self.xq.s, self.xq.bs, self.ff_out, 1,
-                           ssq_in=self.ssq[slot], eps=eps)
-                k.swiglu_q80(self.ff_out, self.ff_out[:, c.ff_dim0:],
-                             2 * c.ff_dim0, c.ff_dim0, 1, self.dq.q[:1],
-                             self.dq.s[:1], self.dq.bs[:1],
-                             c.hidden_act == HIDDEN_ACT_GELU)
-                # w2: residual fold + deferred emit for the NEXT layer's
-                # norm0 (final_norm for logits after the last layer)
-                if self.tp_path:
-                    self._tp_proj_deferred(lw["w2"], self.dq,
-                                           self.ssq[slot + 1], wn)
-                elif self.ksplit_resid:
-                    k.q40_gemv_ksplit(lw["w2"].qs, lw["w2"].scales, self.dq.q,
-                                      self.dq.s, self.dq.bs, self.gemm_part,
-                                      self.ksplit_resid)
-                    k.add_ssq_q(x[:1], self.gemm_part, self.ssq[slot + 1],
-                                wn, self.xq.q[:1], self.xq.s[:1],
-                                self.xq.bs[:1], self.ksplit_resid)
-                else:
-                    k.q40_gemv_resid_q(lw["w2"].qs, lw["w2"].scales,
-                                       self.dq.q, self.dq.s, self.dq.bs, x,
-                                       self.ssq[slot + 1], wn, self.xq.q,
-                                       self.xq.s, self.xq.bs)
+                k.q40_gemv(lw["w13"].qs, lw["w13"].scales, *self.xq.triple(),
+                           self.ff_out, 1, ssq_in=self.ssq[slot], eps=eps)
+                self._swiglu_q80(self.ff_out, 1, self.dq,
+                                 c.hidden_act == HIDDEN_ACT_GELU)
+                self._proj_merge_deferred(lw["w2"], self.dq, slot + 1, wn)
             slot += 1
-        use_amax = self.greedy_feedback and not self.tp_path
-        k.q40_gemv(self.wcls.qs, self.wcls.scales, self.xq.q, self.xq.s,
-                   self.xq.bs, self.logits0, 1,
-                   self.amax_scratch if use_amax else None,
-                   ssq_in=self.ssq[slot], eps=eps)
-        if self.tp_path:
-            self.comm.all_gather(self.logits_gather[1], self.logits0[:1])
-        if self.greedy_feedback:
-            if use_amax:
-                k.token_from_argmax(self.tokens, self.amax_scratch,
-                                    self.amax_blocks)
-            else:
-                k.argmax_token(self.tokens, self.logits_gather[1].view(-1),
-                               self.argmax_scratch_full)
+        self._logits(1, 1, slot, deferred=True)
 
-    def _tp_proj_deferred(self, lin: Linear, qb: QuantBuf, ssq_slot,
-                          wnorm: torch.Tensor):
-        """TP down-projection, deferred form: the GEMV epilogue emits the
-        Q80 wire directly, the all-gathered slices merge into x with the
-        next matmul's deferred quant emitted in the same kernel."""
+    def _moe_ffn_deferred(self, lw: dict, slot: int, wn):
+        """MoE deferred FFN: router reads x*norm1*inv directly (no t_norm
+        buffer), grouped w13 consumes the deferred xq, and the scale-merge
+        epilogue emits the NEXT layer's deferred quant — both per-layer
+        norm_quant launches gone here too."""
         c, k = self.cfg, self.k
-        row_bytes = c.dim + 2 * (c.dim // QB)
-        k.q40_gemv_pack(lin.qs, lin.scales, qb.q, qb.s, qb.bs,
-                        self.sync_out[:row_bytes])
-        inb = self.sync_in[1]
-        self.comm.all_gather(inb, self.sync_out[:row_bytes])
-        k.merge_add_q(self.x[:1], inb.view(c.world, 1, row_bytes), ssq_slot,
-                      wnorm, self.xq.q, self.xq.s, self.xq.bs)
+        ka = c.n_active_experts
+        k.router_gemv_norm(lw["gate"], self.x, lw["norm1"], self.ssq[slot],
+                           c.norm_eps, self.moe_router, 1)
+        k.moe_gate(self.moe_router[:1], self.moe_idx, self.moe_wts, 1, ka)
+        k.q40_gemv_grouped(lw["w13"].qs, lw["w13"].scales, *self.xq.triple(),
+                           self.moe_idx[:ka], self.moe_out13, ka,
+                           ssq_in=self.ssq[slot], eps=c.norm_eps)
+        self._swiglu_q80(self.moe_out13, ka, self.moe_dq)
+        k.q40_gemv_grouped(lw["w2"].qs, lw["w2"].scales, *self.moe_dq.triple(),
+                           self.moe_idx[:ka], self.moe_y, 1)
+        if self.tp_path:
+            # expert-weighted sum packed straight into the Q80 wire;
+            # merge-add after the gather folds residual + emits the next
+            # deferred quant
+            k.scale_merge_pack(self.moe_y, self.moe_wts,
+                               self.sync_out[: self.row_bytes], 1, ka, c.dim)
+            self._wire_exchange(1, self.ssq[slot + 1], wn)
+        else:
+            k.scale_merge_add_q(self.x[:1], self.moe_y, self.moe_wts,
+                                self.ssq[slot + 1], wn, *self.xq.triple(),
+                                1, ka)
 
     def _moe_ffn(self, B: int, NB: int, lw: dict, slot: int):
         """Router + grouped expert GEMVs (reference llm.cpp:450-487);
@@ -761,42 +722,33 @@ class HipTransformer:
         ka = c.n_active_experts
         S = NB * ka
         k.router_gemv(lw["gate"], self.t_norm, self.moe_router, NB)
-        if (c.ff_dim0 % 32 == 0 and ka <= 16
-                and getattr(self, "fused_moe", False)):
+        if c.ff_dim0 % 32 == 0 and ka <= 16 and self.fused_moe:
             # gate-fused decode path: every consumer recomputes the
             # deterministic top-k from the router logits in-kernel, so the
             # FFN is 3 launches (w13+swiglu, w2, scale-merge) instead of 6
-            router = self.moe_router[:NB]
+            # and the merge takes the router logits for the expert weights
+            wts, gate = self.moe_router[:NB], {"gate": True}
             k.q40_gemv_grouped_swiglu(lw["w13"].qs, lw["w13"].scales,
-                                      self.xq.q, self.xq.s, self.xq.bs,
-                                      self.moe_dq.q, self.moe_dq.s,
-                                      self.moe_dq.bs, S, router, ka)
-            k.q40_gemv_grouped(lw["w2"].qs, lw["w2"].scales, self.moe_dq.q,
-                               self.moe_dq.s, self.moe_dq.bs,
-                               self.moe_idx[:S], self.moe_y, 1,
-                               router=router, topk=ka, n_slots=S)
-            if not self.tp_path:
-                k.scale_merge_add(self.x[:NB], self.moe_y, router,
-                                  self.ssq[slot], NB, ka, gate=True)
-            else:
-                k.scale_merge(self.partial[:NB], self.moe_y, router, NB, ka,
-                              gate=True)
-                self._sync_partial(NB, slot)
-            return
-        k.moe_gate(self.moe_router[:NB], self.moe_idx, self.moe_wts, NB, ka)
-        k.q40_gemv_grouped(lw["w13"].qs, lw["w13"].scales, self.xq.q, self.xq.s,
-                           self.xq.bs, self.moe_idx[:S], self.moe_out13, ka)
-        k.swiglu_q80(self.moe_out13, self.moe_out13[:, c.ff_dim0:],
-                     2 * c.ff_dim0, c.ff_dim0, S, self.moe_dq.q[:S],
-                     self.moe_dq.s[:S], self.moe_dq.bs[:S])
-        k.q40_gemv_grouped(lw["w2"].qs, lw["w2"].scales, self.moe_dq.q,
-                           self.moe_dq.s, self.moe_dq.bs, self.moe_idx[:S],
-                           self.moe_y, 1)
-        if not self.tp_path:
-            k.scale_merge_add(self.x[:NB], self.moe_y, self.moe_wts,
-                              self.ssq[slot], NB, ka)
+                                      *self.xq.triple(), *self.moe_dq.triple(),
+                                      S, wts, ka)
+            k.q40_gemv_grouped(lw["w2"].qs, lw["w2"].scales,
+                               *self.moe_dq.triple(), self.moe_idx[:S],
+                               self.moe_y, 1, router=wts, topk=ka, n_slots=S)
         else:
-            k.scale_merge(self.partial[:NB], self.moe_y, self.moe_wts, NB, ka)
+            wts, gate = self.moe_wts, {}
+            k.moe_gate(self.moe_router[:NB], self.moe_idx, self.moe_wts, NB, ka)
+            k.q40_gemv_grouped(lw["w13"].qs, lw["w13"].scales,
+                               *self.xq.triple(), self.moe_idx[:S],
+                               self.moe_out13, ka)
+            self._swiglu_q80(self.moe_out13, S, self.moe_dq)
+            k.q40_gemv_grouped(lw["w2"].qs, lw["w2"].scales,
+                               *self.moe_dq.triple(), self.moe_idx[:S],
+                               self.moe_y, 1)
+        if not self.tp_path:
+            k.scale_merge_add(self.x[:NB], self.moe_y, wts, self.ssq[slot],
+                              NB, ka, **gate)
+        else:
+            k.scale_merge(self.partial[:NB], self.moe_y, wts, NB, ka, **gate)
             self._sync_partial(NB, slot)
 
     # ------------------------------------------------------------ engine API
@@ -838,7 +790,6 @@ class HipTransformer:
             self.pos.fill_(p0)
             self._graph_pos = None
             self.forward_buffers(B)
-        c = self.cfg
         if self.tp_path:
             NBp = _pow2_batch(B)
             self.k.logits_concat(self.logits_full, self.logits_gather[NBp], B)
@@ -864,12 +815,8 @@ class HipTransformer:
         graph. Decode state (KV caches, device pos) is untouched; the
         capture warmup's KV write at the current pos is overwritten by the
         next real step."""
-        c = self.cfg
         self.attn_splits = s
-        NB = self.n_batches
-        dev = self.device
-        self.attn_ml = torch.zeros(NB * c.n_heads0 * s * 2, device=dev)
-        self.attn_o = torch.zeros(NB * c.n_heads0 * s * c.head_dim, device=dev)
+        self._alloc_attn_scratch()
         if self._graph is not None:
             pos_saved = int(self.pos.item())
             self.capture_decode_graph()
@@ -877,24 +824,35 @@ class HipTransformer:
             self._graph_pos = pos_saved
         self._pf_graphs.clear()  # prefill graphs also reference the scratch
 
+    def _warm_and_capture(self, B: int, warmups: int, advance_pos: bool = False):
+        """Run forward_buffers(B) `warmups` times on a side stream
+        (allocations, lazy kernel loads), then capture it as a hipGraph;
+        advance_pos appends the device position increment."""
+        torch.cuda.synchronize(self.device)
+        s = torch.cuda.Stream(self.device)
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):
+            for _ in range(warmups):
+                self.forward_buffers(B)
+        torch.cuda.current_stream(self.device).wait_stream(s)
+        torch.cuda.synchronize(self.device)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self.forward_buffers(B)
+            if advance_pos:
+                self.k.pos_inc(self.pos, 1)
+        return g
+
     def _capture_prefill_graph(self, skip_logits: bool):
         try:
-            torch.cuda.synchronize(self.device)
             saved = self.skip_logits
             self.skip_logits = skip_logits
-            s = torch.cuda.Stream(self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(s):
-                self.forward_buffers(self.n_batches)
-            torch.cuda.current_stream(self.device).wait_stream(s)
-            torch.cuda.synchronize(self.device)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self.forward_buffers(self.n_batches)
+            g = self._warm_and_capture(self.n_batches, warmups=1)
             self.skip_logits = saved
             self._pf_graphs[skip_logits] = g
             return g
         except Exception:  # noqa: BLE001
+            # capture unsupported here: prefill chunks run eagerly from now on
             self._pf_failed = True
             self.skip_logits = skip_logits
             return None
@@ -904,17 +862,5 @@ class HipTransformer:
         hipGraph; each subsequent decode costs one graph replay
         (the HIP analog of the reference's recorded Vulkan command buffers,
         nn-vulkan.cpp:1065-1118)."""
-        torch.cuda.synchronize(self.device)
-        s = torch.cuda.Stream(self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            for _ in range(2):  # warmup allocations/kernels on a side stream
-                self.forward_buffers(1)
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self.forward_buffers(1)
-            self.k.pos_inc(self.pos, 1)
-        self._graph = g
+        self._graph = self._warm_and_capture(1, warmups=2, advance_pos=True)
         self._graph_pos = None  # device pos unknown until first fill
