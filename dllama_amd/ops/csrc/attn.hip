@@ -1,0 +1,656 @@
+// dllama_amd — split-K flash-decode attention, rope and KV-cache writes.
+
+#include "dllama_common.h"
+
+// ------------------------------------------------- split-K flash decode
+// Stage 1: grid (H0, B, S); split sp covers t = (sp*4+wave) + 4*S*i — the
+// t-range is spread over S*4 waves so long contexts fill the chip.
+// Per-split (m, l, o) goes to scratch; stage 2 combines the S partials.
+template <int VEC, typename KVT, bool FUSE = false>
+__global__ void k_attn_split(const float *__restrict__ q, int q_ld,
+                             const KVT *__restrict__ kc,
+                             const KVT *__restrict__ vc,
+                             const int *__restrict__ pos,
+                             int n_heads0, int kv_mul, int kv_dim0, float scale,
+                             float *__restrict__ ml_scratch,
+                             float *__restrict__ o_scratch,
+                             int *__restrict__ counter,
+                             float *__restrict__ y,
+                             int8_t *__restrict__ zq,
+                             float *__restrict__ zs,
+                             float *__restrict__ zbs) {
+    (void)counter; (void)y; (void)zq; (void)zs; (void)zbs;
+    const int h0 = blockIdx.x;
+    const int b = blockIdx.y;
+    const int sp = blockIdx.z;
+    const int S = gridDim.z;
+    const int hd = VEC * WAVE;
+    const int plen = pos[0] + b + 1;
+    const int wave = threadIdx.x / WAVE;
+    const int lane = threadIdx.x % WAVE;
+    const int kv_off = (h0 / kv_mul) * hd;
+
+    // Each wave's 4 groups of 16 lanes score 4 timesteps per iteration:
+    // the serial online-softmax chain advances once per 4 t (a 1-t-per-wave
+    // loop measured 22 us at pos=1024 — latency-chained, not memory-bound).
+    const int VEC16 = VEC * 4;  // q/k elems per lane within a 16-lane group
+    const int lane16 = lane & 15;
+    const int group = lane >> 4;
+
+    float qreg[VEC16];
+    #pragma unroll
+    for (int v = 0; v < VEC16; v++)
+        qreg[v] = q[(int64_t)b * q_ld + h0 * hd + lane16 * VEC16 + v] * scale;
+
+    float m = -1e30f, l = 0.0f, o[VEC];
+    #pragma unroll
+    for (int v = 0; v < VEC; v++) o[v] = 0.0f;
+
+    // 4 t-chunks (16 timesteps) per online-softmax round: the K dots of all
+    // 4 chunks are independent, so their HBM loads issue together instead of
+    // serializing behind the softmax chain (the 1-chunk-per-round loop was
+    // latency-bound: ~13 us at pos 1024 for ~1.3 us of KV traffic)
+    const int stride = 16 * S;
+    for (int tb0 = (sp * 4 + wave) * 4; tb0 < plen; tb0 += 4 * stride) {
+        float su[4];
+        #pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int tg = tb0 + u * stride + group;
+            float partial = 0.0f;
+            if (tg < plen) {
+                const KVT *krow = kc + (int64_t)tg * kv_dim0 + kv_off + lane16 * VEC16;
+                #pragma unroll
+                for (int v = 0; v < VEC16; v++)
+                    partial = fmaf(qreg[v], kv_f(krow[v]), partial);
+            }
+            su[u] = group16_reduce_sum(partial);
+        }
+        float s16[16];
+        float mn = m;
+        #pragma unroll
+        for (int u = 0; u < 4; u++) {
+            #pragma unroll
+            for (int gg = 0; gg < 4; gg++) {
+                float v = __shfl(su[u], gg * 16, WAVE);
+                if (tb0 + u * stride + gg >= plen) v = -1e30f;
+                s16[4 * u + gg] = v;
+                mn = fmaxf(mn, v);
+            }
+        }
+        const float f = __expf(m - mn);
+        float w16[16];
+        float lsum = 0.0f;
+        #pragma unroll
+        for (int i = 0; i < 16; i++) {
+            w16[i] = __expf(s16[i] - mn);
+            lsum += w16[i];
+        }
+        l = l * f + lsum;
+        #pragma unroll
+        for (int v = 0; v < VEC; v++) o[v] *= f;
+        #pragma unroll
+        for (int u = 0; u < 4; u++) {
+            #pragma unroll
+            for (int gg = 0; gg < 4; gg++) {
+                const int t = tb0 + u * stride + gg;
+                if (t >= plen) continue;
+                const KVT *vrow = vc + (int64_t)t * kv_dim0 + kv_off + lane * VEC;
+                #pragma unroll
+                for (int v = 0; v < VEC; v++)
+                    o[v] = fmaf(w16[4 * u + gg], kv_f(vrow[v]), o[v]);
+            }
+        }
+        m = mn;
+    }
+
+    __shared__ float sm[4], sl[4];
+    __shared__ float so[4][VEC * WAVE];
+    if (lane == 0) { sm[wave] = m; sl[wave] = l; }
+    __syncthreads();
+    const float M = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+    const float fw = __expf(m - M);
+    #pragma unroll
+    for (int v = 0; v < VEC; v++) so[wave][lane * VEC + v] = o[v] * fw;
+    __syncthreads();
+    const int64_t slot = ((int64_t)b * n_heads0 + h0) * S + sp;
+    if (wave == 0) {
+        const float L = sl[0] * __expf(sm[0] - M) + sl[1] * __expf(sm[1] - M)
+                      + sl[2] * __expf(sm[2] - M) + sl[3] * __expf(sm[3] - M);
+        if constexpr (FUSE) {
+            // S==1 single-kernel path (short contexts): normalize and emit
+            // the Q80 triple of this head directly — no scratch round-trip,
+            // no combine launch (the 2-kernel pair costs ~11 us in-graph at
+            // pos<256 where the actual KV read is microseconds)
+            const float invL = 1.0f / L;
+            float vv[VEC];
+            #pragma unroll
+            for (int v = 0; v < VEC; v++) {
+                const int i = lane * VEC + v;
+                vv[v] = (so[0][i] + so[1][i] + so[2][i] + so[3][i]) * invL;
+            }
+            if constexpr (VEC == 2) {
+                // lane holds elems (2*lane, 2*lane+1): block = 16-lane group,
+                // two values per lane — not the one-per-lane q80_quant_group32
+                const float amax = group16_reduce_max(fmaxf(fabsf(vv[0]), fabsf(vv[1])));
+                const float dd = amax / 127.0f;
+                const float qinv = dd > 0.0f ? 1.0f / dd : 0.0f;
+                const float q0 = rintf(vv[0] * qinv), q1 = rintf(vv[1] * qinv);
+                const int64_t obase = ((int64_t)b * n_heads0 + h0) * hd + lane * 2;
+                zq[obase] = (int8_t)q0;
+                zq[obase + 1] = (int8_t)q1;
+                const float bsum = group16_reduce_sum(q0 + q1);
+                if ((lane & 15) == 0) {
+                    const int blk = (h0 * hd + lane * 2) / QB;
+                    zs[(int64_t)b * (n_heads0 * hd / QB) + blk] = dd;
+                    zbs[(int64_t)b * (n_heads0 * hd / QB) + blk] = bsum;
+                }
+            } else {
+                const Q80Lane c = q80_quant_group32(vv[0]);
+                zq[((int64_t)b * n_heads0 + h0) * hd + lane] = (int8_t)c.qf;
+                const float bsum = group32_reduce_sum(c.qf);
+                if ((lane & 31) == 0) {
+                    const int blk = (h0 * hd + lane) / QB;
+                    zs[(int64_t)b * (n_heads0 * hd / QB) + blk] = c.d;
+                    zbs[(int64_t)b * (n_heads0 * hd / QB) + blk] = bsum;
+                }
+            }
+        } else {
+            if (lane == 0) {
+                ml_scratch[slot * 2] = M;
+                ml_scratch[slot * 2 + 1] = L;
+            }
+            #pragma unroll
+            for (int v = 0; v < VEC; v++) {
+                const int i = lane * VEC + v;
+                o_scratch[slot * hd + i] = so[0][i] + so[1][i] + so[2][i] + so[3][i];
+            }
+        }
+    }
+
+}
+
+// GQA-grouped split variant: one workgroup owns ALL kv_mul query heads of
+// a kv head (wave w = query head kvh*kv_mul+w), so the K/V rows stream
+// through one CU's L1 once instead of kv_mul times through different XCD
+// L2s (4x HBM amplification for 8B's 32q/8kv at long context). Waves are
+// independent heads — no cross-wave merge; each writes its split partial
+// directly. The model scales S by kv_mul to keep the grid full.
+template <int VEC, typename KVT>
+__global__ void k_attn_split_gqa(const float *__restrict__ q, int q_ld,
+                                 const KVT *__restrict__ kc,
+                                 const KVT *__restrict__ vc,
+                                 const int *__restrict__ pos,
+                                 int n_heads0, int kv_mul, int kv_dim0,
+                                 float scale,
+                                 float *__restrict__ ml_scratch,
+                                 float *__restrict__ o_scratch) {
+    const int kvh = blockIdx.x;
+    const int b = blockIdx.y;
+    const int sp = blockIdx.z;
+    const int S = gridDim.z;
+    const int hd = VEC * WAVE;
+    const int plen = pos[0] + b + 1;
+    const int wave = threadIdx.x / WAVE;
+    const int lane = threadIdx.x % WAVE;
+    const int h0 = kvh * kv_mul + wave;
+    const int kv_off = kvh * hd;
+    const int VEC16 = VEC * 4;
+    const int lane16 = lane & 15;
+    const int group = lane >> 4;
+
+    float qreg[VEC16];
+    #pragma unroll
+    for (int v = 0; v < VEC16; v++)
+        qreg[v] = q[(int64_t)b * q_ld + h0 * hd + lane16 * VEC16 + v] * scale;
+
+    float m = -1e30f, l = 0.0f, o[VEC];
+    #pragma unroll
+    for (int v = 0; v < VEC; v++) o[v] = 0.0f;
+
+    // 16 consecutive timesteps per round (4 group-chunks x 4 unrolled);
+    // all waves walk the same rounds, so the wg's K/V reads coalesce in L1
+    for (int tb0 = sp * 16; tb0 < plen; tb0 += 16 * S) {
+        float su[4];
+        #pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int tg = tb0 + u * 4 + group;
+            float partial = 0.0f;
+            if (tg < plen) {
+                const KVT *krow = kc + (int64_t)tg * kv_dim0 + kv_off + lane16 * VEC16;
+                #pragma unroll
+                for (int v = 0; v < VEC16; v++)
+                    partial = fmaf(qreg[v], kv_f(krow[v]), partial);
+            }
+            su[u] = group16_reduce_sum(partial);
+        }
+        float s16[16];
+        float mn = m;
+        #pragma unroll
+        for (int u = 0; u < 4; u++) {
+            #pragma unroll
+            for (int gg = 0; gg < 4; gg++) {
+                float v = __shfl(su[u], gg * 16, WAVE);
+                if (tb0 + u * 4 + gg >= plen) v = -1e30f;
+                s16[4 * u + gg] = v;
+                mn = fmaxf(mn, v);
+            }
+        }
+        const float f = __expf(m - mn);
+        float w16[16];
+        float lsum = 0.0f;
+        #pragma unroll
+        for (int i = 0; i < 16; i++) {
+            w16[i] = __expf(s16[i] - mn);
+            lsum += w16[i];
+        }
+        l = l * f + lsum;
+        #pragma unroll
+        for (int v = 0; v < VEC; v++) o[v] *= f;
+        #pragma unroll
+        for (int u = 0; u < 4; u++) {
+            #pragma unroll
+            for (int gg = 0; gg < 4; gg++) {
+                const int t = tb0 + u * 4 + gg;
+                if (t >= plen) continue;
+                const KVT *vrow = vc + (int64_t)t * kv_dim0 + kv_off + lane * VEC;
+                #pragma unroll
+                for (int v = 0; v < VEC; v++)
+                    o[v] = fmaf(w16[4 * u + gg], kv_f(vrow[v]), o[v]);
+            }
+        }
+        m = mn;
+    }
+
+    const int64_t slot = ((int64_t)b * n_heads0 + h0) * S + sp;
+    if (lane == 0) {
+        ml_scratch[slot * 2] = m;
+        ml_scratch[slot * 2 + 1] = l;
+    }
+    #pragma unroll
+    for (int v = 0; v < VEC; v++)
+        o_scratch[slot * hd + lane * VEC + v] = o[v];
+}
+
+// Stage 2: combine the S split partials. QUANT=true additionally emits the
+// Q80 triple of the attention output directly (each workgroup owns a whole
+// head = hd/32 quant blocks), eliminating the separate cast kernel the
+// reference runs before the wo matmul. (A fused last-block-combine variant
+// measured 2x SLOWER: per-workgroup threadfence + tail serialization.)
+template <int VEC, bool QUANT>
+__global__ void k_attn_combine(const float *__restrict__ ml_scratch,
+                               const float *__restrict__ o_scratch,
+                               float *__restrict__ y,
+                               int8_t *__restrict__ zq,
+                               float *__restrict__ zs,
+                               float *__restrict__ zbs,
+                               int n_heads0, int S) {
+    const int h0 = blockIdx.x;
+    const int b = blockIdx.y;
+    const int hd = VEC * WAVE;  // blockDim.x == hd
+    const int64_t base = ((int64_t)b * n_heads0 + h0) * S;
+    float M = -1e30f;
+    for (int sp = 0; sp < S; sp++)
+        M = fmaxf(M, ml_scratch[(base + sp) * 2]);
+    float L = 0.0f;
+    for (int sp = 0; sp < S; sp++)
+        L += ml_scratch[(base + sp) * 2 + 1] * __expf(ml_scratch[(base + sp) * 2] - M);
+    const float invL = 1.0f / L;
+    const int i = threadIdx.x;
+    float acc = 0.0f;
+    for (int sp = 0; sp < S; sp++)
+        acc += o_scratch[(base + sp) * hd + i]
+             * __expf(ml_scratch[(base + sp) * 2] - M);
+    const float v = acc * invL;
+    if (!QUANT) {
+        y[((int64_t)b * n_heads0 + h0) * hd + i] = v;
+    } else {
+        const Q80Lane c = q80_quant_group32(v);
+        zq[((int64_t)b * n_heads0 + h0) * hd + i] = (int8_t)c.qf;
+        const float bsum = group32_reduce_sum(c.qf);
+        if ((i & 31) == 0) {
+            const int blk = (h0 * hd + i) / QB;
+            zs[(int64_t)b * (n_heads0 * hd / QB) + blk] = c.d;
+            zbs[(int64_t)b * (n_heads0 * hd / QB) + blk] = bsum;
+        }
+    }
+}
+
+// ------------------------------------------------------------------ rope
+// style 0 = llama interleaved pairs (reference ropeLlama_F32,
+// nn-cpu-ops.cpp:843-863), style 1 = falcon/neox half-rotated
+// (ropeFalcon_F32, :865-885). cache [seq, hd/2, 2] = (cos, sin).
+// x [B, dim0]; row b uses position pos[0]+b.
+template <int STYLE>
+__global__ void k_rope(float *__restrict__ x,
+                       const float *__restrict__ cache,
+                       const int *__restrict__ pos,
+                       int dim0, int hd) {
+    const int b = blockIdx.y;
+    const int p = pos[0] + b;
+    const int half = hd >> 1;
+    float *row = x + (int64_t)b * dim0;
+    const float *pc = cache + (int64_t)p * hd;  // hd floats = hd/2 pairs
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < dim0 / 2;
+         i += gridDim.x * blockDim.x) {
+        const int head = i / half;
+        const int j = i % half;  // cache pair index
+        int i0, i1;
+        if (STYLE == 0) {          // pair (2j, 2j+1) within each head
+            i0 = head * hd + 2 * j;
+            i1 = i0 + 1;
+        } else {                   // pair (j, j+hd/2) within each head
+            i0 = head * hd + j;
+            i1 = i0 + half;
+        }
+        const float cr = pc[2 * j];
+        const float ci = pc[2 * j + 1];
+        const float v0 = row[i0];
+        const float v1 = row[i1];
+        row[i0] = v0 * cr - v1 * ci;
+        row[i1] = v0 * ci + v1 * cr;
+    }
+}
+
+// ------------------------------------------- fused rope(q,k) + kv append
+// Operates directly on the fused QKV GEMV output buffer ([B, ld] with
+// q | k | v packed per row): rotates q in place, rotates k and writes it to
+// the cache row pos+b, and copies v to the cache — one launch replacing
+// rope(q), rope(k), kv_append (reference runs 4 separate ops here,
+// llm.cpp:300-330).
+template <int STYLE, typename KVT>
+__global__ void k_rope_kv(float *__restrict__ qkv, int ld,
+                          int q_dim0, int kv_dim0,
+                          const float *__restrict__ cache,
+                          const int *__restrict__ pos,
+                          KVT *__restrict__ kc,
+                          KVT *__restrict__ vc,
+                          int hd) {
+    const int b = blockIdx.y;
+    const int p = pos[0] + b;
+    const int half = hd >> 1;
+    const float *pc = cache + (int64_t)p * hd;
+    float *qrow = qkv + (int64_t)b * ld;
+    float *krow = qrow + q_dim0;
+    const float *vrow = krow + kv_dim0;
+    const int qp = q_dim0 >> 1, kp = kv_dim0 >> 1, vq = kv_dim0 >> 2;
+    const int total = qp + kp + vq;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += gridDim.x * blockDim.x) {
+        if (i < qp + kp) {
+            const bool is_q = i < qp;
+            const int ii = is_q ? i : i - qp;
+            const int head = ii / half;
+            const int j = ii % half;
+            int i0, i1;
+            if (STYLE == 0) { i0 = head * hd + 2 * j; i1 = i0 + 1; }
+            else            { i0 = head * hd + j;     i1 = i0 + half; }
+            const float cr = pc[2 * j];
+            const float ci = pc[2 * j + 1];
+            float *src = is_q ? qrow : krow;
+            const float v0 = src[i0];
+            const float v1 = src[i1];
+            const float o0 = v0 * cr - v1 * ci;
+            const float o1 = v0 * ci + v1 * cr;
+            if (is_q) { src[i0] = o0; src[i1] = o1; }
+            else {
+                KVT *dst = kc + (int64_t)p * kv_dim0;
+                dst[i0] = kv_c<KVT>(o0); dst[i1] = kv_c<KVT>(o1);
+            }
+        } else {
+            const int j = (i - qp - kp) * 4;
+            const float4 vv = *reinterpret_cast<const float4 *>(vrow + j);
+            KVT *dst = vc + (int64_t)p * kv_dim0 + j;
+            dst[0] = kv_c<KVT>(vv.x); dst[1] = kv_c<KVT>(vv.y);
+            dst[2] = kv_c<KVT>(vv.z); dst[3] = kv_c<KVT>(vv.w);
+        }
+    }
+}
+
+// ------------------------------------------------------------------ kv append
+// copy k,v batch rows into the caches at row pos[0]+b (reference OP_SHIFT,
+// nn-cpu-ops.cpp:1419-1441).
+template <typename KVT>
+__global__ void k_kv_append(const float *__restrict__ k,
+                            const float *__restrict__ v,
+                            KVT *__restrict__ kc,
+                            KVT *__restrict__ vc,
+                            const int *__restrict__ pos,
+                            int kv_dim0) {
+    const int b = blockIdx.y;
+    const int p = pos[0] + b;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < kv_dim0;
+         i += gridDim.x * blockDim.x) {
+        kc[(int64_t)p * kv_dim0 + i] = kv_c<KVT>(k[(int64_t)b * kv_dim0 + i]);
+        vc[(int64_t)p * kv_dim0 + i] = kv_c<KVT>(v[(int64_t)b * kv_dim0 + i]);
+    }
+}
+
+// Qwen3 attention prologue in one launch: per-head rmsnorm of the q/k heads
+// (reference OP_RMS_NORM nColumns mode, llm.cpp:178-187) + neox rope + KV
+// cache write (reference rope + shift ops). One workgroup (1 wave) per head:
+// q heads normalize+rotate in place, k heads normalize+rotate into the
+// cache, v heads copy to the cache.
+template <typename KVT>
+__global__ void k_rope_kv_qknorm(float *__restrict__ qkv, int ld,
+                                 int q_dim0, int kv_dim0,
+                                 const float *__restrict__ cache,
+                                 const int *__restrict__ pos,
+                                 KVT *__restrict__ kc, KVT *__restrict__ vc,
+                                 int hd,
+                                 const float *__restrict__ wq,
+                                 const float *__restrict__ wk, float eps) {
+    const int b = blockIdx.y;
+    const int p = pos[0] + b;
+    const int h = blockIdx.x;
+    const int qh = q_dim0 / hd, kvh = kv_dim0 / hd;
+    const int half = hd >> 1;
+    const float *pc = cache + (int64_t)p * hd;
+    const int lane = threadIdx.x;  // blockDim == 64
+    if (h >= qh + kvh) {
+        // v head: plain copy into the cache
+        const int hv = h - qh - kvh;
+        const float *src = qkv + (int64_t)b * ld + q_dim0 + kv_dim0 + hv * hd;
+        KVT *dst = vc + (int64_t)p * kv_dim0 + hv * hd;
+        for (int i = lane; i < hd; i += WAVE) dst[i] = kv_c<KVT>(src[i]);
+        return;
+    }
+    const bool is_q = h < qh;
+    float *row = qkv + (int64_t)b * ld + (is_q ? h * hd
+                                               : q_dim0 + (h - qh) * hd);
+    const float *w = is_q ? wq : wk;
+    float acc = 0.0f;
+    for (int i = lane; i < hd; i += WAVE) {
+        const float v = row[i];
+        acc += v * v;
+    }
+    acc = wave_reduce_sum(acc);
+    const float inv = rsqrtf(acc / hd + eps);
+    for (int j = lane; j < half; j += WAVE) {
+        const float v0 = row[j] * inv * w[j];
+        const float v1 = row[j + half] * inv * w[j + half];
+        const float cr = pc[2 * j], ci = pc[2 * j + 1];
+        const float o0 = v0 * cr - v1 * ci;
+        const float o1 = v0 * ci + v1 * cr;
+        if (is_q) {
+            row[j] = o0;
+            row[j + half] = o1;
+        } else {
+            KVT *dst = kc + (int64_t)p * kv_dim0 + (h - qh) * hd;
+            dst[j] = kv_c<KVT>(o0);
+            dst[j + half] = kv_c<KVT>(o1);
+        }
+    }
+}
+
+// ============================================================== host bindings
+
+// f(kc, vc) with the cache pointers typed by the cache dtype: __half * (the
+// default) or float *. KVT inside f: std::remove_pointer_t<decltype(kc)>.
+template <typename F>
+static void with_kv_ptrs(torch::Tensor &kc, torch::Tensor &vc, F &&f) {
+    if (kc.scalar_type() == at::kHalf)
+        f(reinterpret_cast<__half *>(kc.data_ptr<at::Half>()),
+          reinterpret_cast<__half *>(vc.data_ptr<at::Half>()));
+    else
+        f(kc.data_ptr<float>(), vc.data_ptr<float>());
+}
+
+// f(VEC) with VEC = head_dim / 64 (elements per lane of the head's wave) as
+// a std::integral_constant
+template <typename F>
+static void with_head_vec(int64_t head_dim, F &&f) {
+    if (head_dim == 128) f(std::integral_constant<int, 2>{});
+    else if (head_dim == 64) f(std::integral_constant<int, 1>{});
+    else TORCH_CHECK(false, "unsupported head_dim ", head_dim);
+}
+
+void rope(torch::Tensor x, torch::Tensor cache, torch::Tensor pos,
+          int64_t head_dim, int64_t style) {
+    CHECK_CUDA(x);
+    const int B = x.size(0);
+    const int dim0 = x.size(1);
+    const dim3 grid(ceil_div(dim0 / 2, 256), B);
+    if (style == 0)
+        hipLaunchKernelGGL(k_rope<0>, grid, dim3(256), 0, cur_stream(),
+                           x.data_ptr<float>(), cache.data_ptr<float>(),
+                           pos.data_ptr<int>(), dim0, (int)head_dim);
+    else
+        hipLaunchKernelGGL(k_rope<1>, grid, dim3(256), 0, cur_stream(),
+                           x.data_ptr<float>(), cache.data_ptr<float>(),
+                           pos.data_ptr<int>(), dim0, (int)head_dim);
+}
+
+void kv_append(torch::Tensor k, torch::Tensor v, torch::Tensor kc,
+               torch::Tensor vc, torch::Tensor pos) {
+    CHECK_CUDA(k);
+    const int B = k.size(0);
+    const int kv_dim0 = k.size(1);
+    const dim3 grid(ceil_div(kv_dim0, 256), B);
+    with_kv_ptrs(kc, vc, [&](auto *kcp, auto *vcp) {
+        using KVT = std::remove_pointer_t<decltype(kcp)>;
+        hipLaunchKernelGGL(k_kv_append<KVT>, grid, dim3(256), 0, cur_stream(),
+                           k.data_ptr<float>(), v.data_ptr<float>(), kcp, vcp,
+                           pos.data_ptr<int>(), kv_dim0);
+    });
+}
+
+void attn(torch::Tensor q, int64_t q_ld, torch::Tensor kc, torch::Tensor vc,
+          torch::Tensor y, torch::Tensor pos, int64_t batch, int64_t n_heads0,
+          int64_t kv_mul, int64_t head_dim, int64_t splits,
+          torch::Tensor ml_scratch, torch::Tensor o_scratch, torch::Tensor counter,
+          c10::optional<torch::Tensor> zq = c10::nullopt,
+          c10::optional<torch::Tensor> zs = c10::nullopt,
+          c10::optional<torch::Tensor> zbs = c10::nullopt) {
+    CHECK_CUDA(q);
+    const int kv_dim0 = kc.size(1);
+    const float scale = 1.0f / sqrtf((float)head_dim);
+    const dim3 grid(n_heads0, batch, splits);
+    const dim3 cgrid(n_heads0, batch);
+    const bool quant = zq.has_value();
+    // quant: the Q80 triple is the output, y is not written (and vice versa)
+    float *yp = quant ? nullptr : y.data_ptr<float>();
+    int8_t *zqp = quant ? zq->data_ptr<int8_t>() : nullptr;
+    float *zsp = quant ? zs->data_ptr<float>() : nullptr;
+    float *zbsp = quant ? zbs->data_ptr<float>() : nullptr;
+    // GQA grouping experiment: one wg per (kv head, split) with kv_mul
+    // waves sharing the K/V stream through L1. Measured ~20% SLOWER
+    // end-to-end (448 vs 545 tok/s short-ctx 8B; MoE 366->255) — the L2
+    // already absorbs the GQA re-reads and the grown combine fan-in costs
+    // more than the saved traffic. Kept behind DLLAMA_GQA_ATTN=1.
+    static const bool env_gqa =
+        std::getenv("DLLAMA_GQA_ATTN") && atoi(std::getenv("DLLAMA_GQA_ATTN")) == 1;
+    const bool gqa = env_gqa && kv_mul > 1 && kv_mul <= 8
+        && n_heads0 % kv_mul == 0 && splits > 1;
+    // splits==1 + quant output: single fused kernel (normalize + Q80 emit
+    // in the split kernel), no combine launch
+    const bool fused = !gqa && splits == 1 && quant;
+    with_head_vec(head_dim, [&](auto vec_const) {
+        constexpr int V = decltype(vec_const)::value;
+        with_kv_ptrs(kc, vc, [&](auto *kcp, auto *vcp) {
+            using KVT = std::remove_pointer_t<decltype(kcp)>;
+            auto split = [&](auto fuse_const) {
+                constexpr bool FUSE = decltype(fuse_const)::value;
+                hipLaunchKernelGGL((k_attn_split<V, KVT, FUSE>), grid, dim3(256), 0,
+                                   cur_stream(), q.data_ptr<float>(), (int)q_ld,
+                                   kcp, vcp, pos.data_ptr<int>(),
+                                   (int)n_heads0, (int)kv_mul, kv_dim0, scale,
+                                   ml_scratch.data_ptr<float>(),
+                                   o_scratch.data_ptr<float>(),
+                                   counter.data_ptr<int>(), nullptr,
+                                   FUSE ? zqp : nullptr, FUSE ? zsp : nullptr,
+                                   FUSE ? zbsp : nullptr);
+            };
+            if (gqa)
+                hipLaunchKernelGGL((k_attn_split_gqa<V, KVT>),
+                                   dim3(n_heads0 / kv_mul, batch, splits),
+                                   dim3(kv_mul * WAVE), 0,
+                                   cur_stream(), q.data_ptr<float>(), (int)q_ld,
+                                   kcp, vcp, pos.data_ptr<int>(), (int)n_heads0,
+                                   (int)kv_mul, kv_dim0, scale,
+                                   ml_scratch.data_ptr<float>(),
+                                   o_scratch.data_ptr<float>());
+            else if (fused)
+                split(std::true_type{});
+            else
+                split(std::false_type{});
+        });
+        if (fused) return;
+        auto combine = [&](auto quant_const) {
+            hipLaunchKernelGGL((k_attn_combine<V, decltype(quant_const)::value>),
+                               cgrid, dim3(V * WAVE), 0, cur_stream(),
+                               ml_scratch.data_ptr<float>(),
+                               o_scratch.data_ptr<float>(), yp, zqp, zsp, zbsp,
+                               (int)n_heads0, (int)splits);
+        };
+        if (quant) combine(std::true_type{});
+        else combine(std::false_type{});
+    });
+}
+
+void rope_kv(torch::Tensor qkv, int64_t ld, int64_t q_dim0, int64_t kv_dim0,
+             torch::Tensor cache, torch::Tensor pos, torch::Tensor kc,
+             torch::Tensor vc, int64_t head_dim, int64_t style, int64_t batch) {
+    CHECK_CUDA(qkv);
+    const int total = (int)(q_dim0 / 2 + kv_dim0 / 2 + kv_dim0 / 4);
+    const dim3 grid(ceil_div(total, 256), batch);
+    with_kv_ptrs(kc, vc, [&](auto *kcp, auto *vcp) {
+        using KVT = std::remove_pointer_t<decltype(kcp)>;
+        auto *kern = style == 0 ? k_rope_kv<0, KVT> : k_rope_kv<1, KVT>;
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, cur_stream(),
+                           qkv.data_ptr<float>(), (int)ld, (int)q_dim0, (int)kv_dim0,
+                           cache.data_ptr<float>(), pos.data_ptr<int>(),
+                           kcp, vcp, (int)head_dim);
+    });
+}
+
+void rope_kv_qknorm(torch::Tensor qkv, int64_t ld, int64_t q_dim0,
+                    int64_t kv_dim0, torch::Tensor cache, torch::Tensor pos,
+                    torch::Tensor kc, torch::Tensor vc, int64_t head_dim,
+                    torch::Tensor wq, torch::Tensor wk, double eps,
+                    int64_t batch) {
+    CHECK_CUDA(qkv);
+    const int heads = (int)((q_dim0 + 2 * kv_dim0) / head_dim);
+    const dim3 grid(heads, batch);
+    with_kv_ptrs(kc, vc, [&](auto *kcp, auto *vcp) {
+        using KVT = std::remove_pointer_t<decltype(kcp)>;
+        hipLaunchKernelGGL((k_rope_kv_qknorm<KVT>), grid, dim3(WAVE), 0,
+                           cur_stream(), qkv.data_ptr<float>(), (int)ld,
+                           (int)q_dim0, (int)kv_dim0, cache.data_ptr<float>(),
+                           pos.data_ptr<int>(), kcp, vcp, (int)head_dim,
+                           wq.data_ptr<float>(), wk.data_ptr<float>(),
+                           (float)eps);
+    });
+}
+
+void register_attn(py::module &m) {
+    m.def("rope_kv_qknorm", &rope_kv_qknorm);
+    m.def("rope", &rope);
+    m.def("rope_kv", &rope_kv);
+    m.def("kv_append", &kv_append);
+    m.def("attn", &attn, py::arg("q"), py::arg("q_ld"), py::arg("kc"), py::arg("vc"),
+          py::arg("y"), py::arg("pos"), py::arg("batch"), py::arg("n_heads0"),
+          py::arg("kv_mul"), py::arg("head_dim"), py::arg("splits"),
+          py::arg("ml_scratch"), py::arg("o_scratch"), py::arg("counter"),
+          py::arg("zq") = py::none(), py::arg("zs") = py::none(),
+          py::arg("zbs") = py::none());
+}

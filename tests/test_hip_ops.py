@@ -2,6 +2,8 @@
 (the role of reference nn-vulkan-test.cpp / nn-cpu-ops-test.cpp:126-277:
 quantized kernels checked against f32 kernels as ground truth)."""
 
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -659,3 +661,246 @@ def test_moe_gate_fused_consumers(k):
     k.scale_merge_add(xa, y2a, wts, ssq[0], B, ka)
     k.scale_merge_add(xb, y2a, router, ssq[1], B, ka, gate=True)
     assert torch.allclose(xb, xa, atol=1e-5)
+
+
+# ---------------------------------------------------------------------------
+# Fused Q80-emitting epilogues vs the tested ops they replace. Where both
+# sides run the same device arithmetic on the same values the comparison is
+# bit-exact; where the summation order differs the file's tolerances apply
+# (codes +-1, scales 1e-6, dequantized amax/100, blocksums 2.0).
+
+EPS = 1e-5
+
+
+@functools.lru_cache(maxsize=None)
+def _linear(d, n, seed):
+    return _mk_linear(d, n, seed)
+
+
+def _q80_bufs(rows, n):
+    return (torch.zeros(rows, n, dtype=torch.int8, device=DEV),
+            torch.zeros(rows, n // 32, device=DEV),
+            torch.zeros(rows, n // 32, device=DEV))
+
+
+def _q80(k, x):
+    out = _q80_bufs(*x.shape)
+    k.q80_quantize(x.contiguous(), *out)
+    return out
+
+
+def _ssq_buf(rows):
+    return torch.zeros(rows, 16 * 32, device=DEV)
+
+
+def _ssq_total(ssq):
+    return ssq.cpu().reshape(-1, 16, 32)[:, :, 0].sum(-1)
+
+
+def _ssq_of(x):
+    """spread-slot ssq buffer holding sum(x^2) per row (all in slot 0)."""
+    ssq = _ssq_buf(x.shape[0])
+    ssq[:, 0] = (x * x).sum(-1)
+    return ssq
+
+
+def _wire_bytes(n):
+    return n + 2 * (n // 32)
+
+
+def _assert_triple_equal(got, want):
+    for name, g, w in zip(("codes", "scales", "blocksums"), got, want):
+        assert torch.equal(g, w), \
+            (name, (g.float() - w.float()).abs().max().item())
+
+
+def _assert_triple_close(got, want):
+    gq, gs, gbs = (t.cpu() for t in got)
+    wq, ws, wbs = (t.cpu() for t in want)
+    assert (gq.int() - wq.int()).abs().max() <= 1
+    assert torch.allclose(gs, ws, atol=1e-6), (gs - ws).abs().max().item()
+    dq, dw = R.q80_dequantize(gq, gs), R.q80_dequantize(wq, ws)
+    assert torch.allclose(dq, dw, atol=dw.abs().max().item() / 100)
+    assert torch.allclose(gbs, wbs, atol=2.0), (gbs - wbs).abs().max().item()
+
+
+def test_q40_gemv_resid_q(k):
+    """RESID_Q epilogue == gemv_resid, then Q80 of x*wnorm (deferred scale);
+    its consumer q40_gemv(ssq_in=) == norm_quant + plain gemv."""
+    d, n = 96, 160  # 3 workgroups of 32 rows, odd block count, 2 block pairs
+    qs, sc, _ = _linear(d, n, 600)
+    xin = _q80(k, rand(1, n, seed=601, scale=0.5))
+    x0 = rand(1, d, seed=602)
+    wnorm = rand(d, seed=603).abs() + 0.5
+    xa, ssq_a = x0.clone(), _ssq_buf(1)
+    k.q40_gemv_resid(qs, sc, *xin, xa, ssq_a, 1)
+    xb, ssq_b, out = x0.clone(), _ssq_buf(1), _q80_bufs(1, d)
+    k.q40_gemv_resid_q(qs, sc, *xin, xb, ssq_b, wnorm, *out)
+    assert torch.equal(xb, xa), (xb - xa).abs().max().item()
+    want_ssq = (xa.cpu() ** 2).sum(-1)
+    assert torch.allclose(_ssq_total(ssq_a), want_ssq, rtol=1e-4)
+    assert torch.allclose(_ssq_total(ssq_b), want_ssq, rtol=1e-4)
+    _assert_triple_equal(out, _q80(k, xb * wnorm))
+    # consumer: deferred triple + ssq_in vs the separate norm_quant
+    qs2, sc2, wref2 = _linear(72, d, 604)
+    nq = _q80_bufs(1, d)
+    k.norm_quant(xb, wnorm, ssq_b, *nq, 1, EPS)
+    y_want = torch.zeros(1, 72, device=DEV)
+    k.q40_gemv(qs2, sc2, *nq, y_want, 1)
+    y_got = torch.zeros(1, 72, device=DEV)
+    k.q40_gemv(qs2, sc2, *out, y_got, 1, None, ssq_b, EPS)
+    f32 = R.q40_matmul(R.rms_norm(xb.cpu(), wnorm.cpu(), EPS), wref2)
+    tol = f32.abs().max().item() * 0.02 + 1e-3
+    assert torch.allclose(y_got, y_want, atol=tol), \
+        (y_got - y_want).abs().max().item()
+    assert torch.allclose(y_got.cpu(), f32, atol=tol)
+
+
+@pytest.mark.parametrize("d", [96, 72, 69])
+@pytest.mark.parametrize("B", [1, 2, 4])
+def test_q40_gemv_ssq_in(k, B, d):
+    """Plain and deferred-scale (ssq_in) GEMV, RPW 1 (B=1) and 2; d=72 and
+    d=69 end in a partially valid workgroup, d=69 also in a half-valid wave."""
+    n = 160
+    qs, sc, wref = _linear(d, n, 610 + d)
+    x = rand(B, n, seed=611 + B)
+    wnorm = rand(n, seed=612).abs() + 0.5
+    ssq = _ssq_of(x)
+    want = R.q40_matmul(R.rms_norm(x.cpu(), wnorm.cpu(), EPS), wref)
+    tol = want.abs().max().item() * 0.02 + 1e-3
+    plain, deferred = _q80_bufs(B, n), _q80_bufs(B, n)
+    k.norm_quant(x, wnorm, ssq, *plain, B, EPS)
+    k.norm_quant(x, wnorm, ssq, *deferred, B, EPS, None, True)
+    y0 = torch.full((B, d), 7.0, device=DEV)
+    k.q40_gemv(qs, sc, *plain, y0, B)
+    y1 = torch.full((B, d), 7.0, device=DEV)
+    k.q40_gemv(qs, sc, *deferred, y1, B, None, ssq, EPS)
+    assert torch.allclose(y0.cpu(), want, atol=tol), \
+        (y0.cpu() - want).abs().max().item()
+    assert torch.allclose(y1.cpu(), want, atol=tol), \
+        (y1.cpu() - want).abs().max().item()
+    assert torch.allclose(y1, y0, atol=tol), (y1 - y0).abs().max().item()
+
+
+@pytest.mark.parametrize("B,n", [(1, 160), (2, 160), (2, 512)])
+def test_norm_quant_deferred(k, B, n):
+    """deferred=True emits x*w with inv_rms left out of the scale: same
+    codes, scale*inv_rms == the plain scale, yout likewise."""
+    x = rand(B, n, seed=620 + n)
+    w = rand(n, seed=621).abs() + 0.5
+    ssq = _ssq_of(x)
+    inv = torch.rsqrt((x * x).sum(-1, keepdim=True) / n + EPS)
+    plain, deferred = _q80_bufs(B, n), _q80_bufs(B, n)
+    y_plain, y_def = torch.zeros(B, n, device=DEV), torch.zeros(B, n, device=DEV)
+    k.norm_quant(x, w, ssq, *plain, B, EPS, y_plain, False)
+    k.norm_quant(x, w, ssq, *deferred, B, EPS, y_def, True)
+    want = R.rms_norm(x.cpu(), w.cpu(), EPS)
+    assert torch.allclose(y_plain.cpu(), want, atol=1e-4, rtol=1e-4)
+    assert torch.equal(y_def, x * w)
+    dq, ds, dbs = deferred
+    _assert_triple_close((dq, ds * inv, dbs), plain)
+    got = R.q80_dequantize(dq.cpu(), (ds * inv).cpu())
+    assert torch.allclose(got, want, atol=want.abs().max().item() / 100)
+
+
+def test_q40_gemv_pack(k):
+    """PACK epilogue == plain gemv + sync_quant_pack, byte for byte."""
+    d, n = 96, 160
+    qs, sc, _ = _linear(d, n, 630)
+    xin = _q80(k, rand(1, n, seed=631, scale=0.5))
+    y = torch.zeros(1, d, device=DEV)
+    k.q40_gemv(qs, sc, *xin, y, 1)
+    want = torch.zeros(_wire_bytes(d), dtype=torch.uint8, device=DEV)
+    k.sync_quant_pack(y, want)
+    got = torch.zeros_like(want)
+    k.q40_gemv_pack(qs, sc, *xin, got)
+    assert torch.equal(got, want), (got.int() - want.int()).abs().max().item()
+
+
+@pytest.mark.parametrize("ks", [2, 3])
+@pytest.mark.parametrize("d", [256, 512])
+def test_q40_gemv_ksplit_add_ssq_q(k, d, ks):
+    """K-split GEMV + add_ssq_q == the RESID_Q epilogue up to summation
+    order (n=160 has two block pairs, so ks=3 leaves one slice empty)."""
+    n = 160
+    qs, sc, _ = _linear(d, n, 640 + d)
+    xin = _q80(k, rand(1, n, seed=641, scale=0.5))
+    x0 = rand(1, d, seed=642)
+    wnorm = rand(d, seed=643).abs() + 0.5
+    xa, ssq_a, want = x0.clone(), _ssq_buf(1), _q80_bufs(1, d)
+    k.q40_gemv_resid_q(qs, sc, *xin, xa, ssq_a, wnorm, *want)
+    part = torch.full((ks, d), 7.0, device=DEV)
+    k.q40_gemv_ksplit(qs, sc, *xin, part, ks)
+    xb, ssq_b, got = x0.clone(), _ssq_buf(1), _q80_bufs(1, d)
+    k.add_ssq_q(xb, part, ssq_b, wnorm, *got, ks)
+    # same products, different f32 summation order: test_q40_gemv's bound
+    # on the GEMV term that was folded into x
+    tol = (xa - x0).abs().max().item() * 0.02 + 1e-3
+    assert torch.allclose(xb, xa, atol=tol), (xb - xa).abs().max().item()
+    assert torch.allclose(_ssq_total(ssq_b), (xb.cpu() ** 2).sum(-1), rtol=1e-4)
+    assert torch.allclose(_ssq_total(ssq_b), _ssq_total(ssq_a), rtol=1e-4)
+    _assert_triple_equal(got, _q80(k, xb * wnorm))
+    _assert_triple_close(got, want)
+
+
+def _wire(k, world, rows, n, seed):
+    """all-gather payload [world, rows, row_bytes] from random partials."""
+    bufs = torch.zeros(world, rows, _wire_bytes(n), dtype=torch.uint8, device=DEV)
+    for w in range(world):
+        k.sync_quant_pack(rand(rows, n, seed=seed + w), bufs[w])
+    return bufs
+
+
+@pytest.mark.parametrize("rows", [1, 2])
+@pytest.mark.parametrize("n", [256, 512])
+def test_merge_add_q(k, n, rows):
+    """merge_add_q == merge_add(ssq=), then Q80 of x*wnorm."""
+    world = 2
+    bufs = _wire(k, world, rows, n, 650)
+    x0 = rand(rows, n, seed=653)
+    wnorm = rand(n, seed=654).abs() + 0.5
+    xa, ssq_a = x0.clone(), _ssq_buf(rows)
+    k.merge_add(xa, bufs, ssq_a)
+    xb, ssq_b, got = x0.clone(), _ssq_buf(rows), _q80_bufs(rows, n)
+    k.merge_add_q(xb, bufs, ssq_b, wnorm, *got)
+    assert torch.equal(xb, xa), (xb - xa).abs().max().item()
+    want_ssq = (xa.cpu() ** 2).sum(-1)
+    assert torch.allclose(_ssq_total(ssq_a), want_ssq, rtol=1e-4)
+    assert torch.allclose(_ssq_total(ssq_b), want_ssq, rtol=1e-4)
+    _assert_triple_equal(got, _q80(k, xb * wnorm))
+
+
+@pytest.mark.parametrize("rows", [1, 2])
+@pytest.mark.parametrize("n", [256, 512])
+def test_scale_merge_pack(k, n, rows):
+    """scale_merge_pack == scale_merge + sync_quant_pack, byte for byte."""
+    topk = 2
+    y = rand(rows * topk, n, seed=660)
+    wts = rand(rows, topk, seed=661).abs()
+    partial = torch.zeros(rows, n, device=DEV)
+    k.scale_merge(partial, y, wts, rows, topk)
+    want = torch.zeros(rows, _wire_bytes(n), dtype=torch.uint8, device=DEV)
+    k.sync_quant_pack(partial, want)
+    got = torch.zeros_like(want)
+    k.scale_merge_pack(y, wts, got, rows, topk, n)
+    assert torch.equal(got, want), (got.int() - want.int()).abs().max().item()
+
+
+@pytest.mark.parametrize("rows", [1, 2])
+@pytest.mark.parametrize("n", [256, 512])
+def test_scale_merge_add_q(k, n, rows):
+    """scale_merge_add_q == scale_merge_add, then Q80 of x*wnorm."""
+    topk = 2
+    y = rand(rows * topk, n, seed=670)
+    wts = rand(rows, topk, seed=671).abs()
+    x0 = rand(rows, n, seed=672)
+    wnorm = rand(n, seed=673).abs() + 0.5
+    xa, ssq_a = x0.clone(), _ssq_buf(rows)
+    k.scale_merge_add(xa, y, wts, ssq_a, rows, topk)
+    xb, ssq_b, got = x0.clone(), _ssq_buf(rows), _q80_bufs(rows, n)
+    k.scale_merge_add_q(xb, y, wts, ssq_b, wnorm, *got, rows, topk)
+    assert torch.equal(xb, xa), (xb - xa).abs().max().item()
+    want_ssq = (xa.cpu() ** 2).sum(-1)
+    assert torch.allclose(_ssq_total(ssq_a), want_ssq, rtol=1e-4)
+    assert torch.allclose(_ssq_total(ssq_b), want_ssq, rtol=1e-4)
+    _assert_triple_equal(got, _q80(k, xb * wnorm))

@@ -1,6 +1,6 @@
 // Round-2 probe: f16 KV cache for split-K decode attention (NOT runtime code).
 //
-// Production attention (k_attn_split/combine in dllama_kernels.hip) reads
+// Production attention (k_attn_split/combine in dllama_amd/ops/csrc/attn.hip) reads
 // f32 KV — parity with the reference's f32 cache (nn-core.cpp:211-218).
 // At long positions the decode attention is KV-bandwidth-bound (17 us at
 // pos 4096, profiles/r01 notes); an f16 cache halves that traffic.

@@ -1,7 +1,7 @@
 // Round-2 prefill-GEMM prototype probe (NOT part of the runtime build).
 //
 // Standalone: self-checks numerics vs a CPU int reference and times the
-// current production kernel (v1, copied from dllama_kernels.hip:909) against
+// current production kernel (v1, copied from k_q40_gemm in dllama_amd/ops/csrc/gemm.hip) against
 // the v2 prototype. Build:
 //   hipcc --offload-arch=gfx950 -O3 tools/gemm_v2_probe.hip -o /tmp/gemm_v2
 // Run (GPU box):

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Per-kernel resource usage (VGPR/SGPR/AGPR/LDS/spill/occupancy) from the
-built extension's embedded gfx950 code object. Works without a GPU.
+built extension's embedded gfx950 code objects. Works without a GPU.
+
+The extension is linked from one translation unit per kernel family, and
+each contributes its own __CLANG_OFFLOAD_BUNDLE__; all of them are read.
 
 Occupancy on CDNA4: VGPRs+AGPRs come from one 512-register file per SIMD;
 waves/SIMD ~= 512 // (vgpr+agpr rounded up to 8), capped at 8 by LDS
@@ -14,26 +17,32 @@ import struct
 import subprocess
 import sys
 import os
+import tempfile
 
 LLVM = "/opt/rocm/lib/llvm/bin"
+MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 
-def extract_hsaco(so_path: str) -> bytes:
+def extract_hsacos(so_path: str) -> list:
+    """The gfx950 code object of every offload bundle in the library."""
     data = open(so_path, "rb").read()
-    off = data.find(b"__CLANG_OFFLOAD_BUNDLE__")
-    if off < 0:
-        raise SystemExit(f"no offload bundle in {so_path}")
-    p = off + 24
-    n, = struct.unpack_from("<Q", data, p)
-    p += 8
-    for _ in range(n):
-        eoff, esz, idl = struct.unpack_from("<QQQ", data, p)
-        p += 24
-        ident = data[p: p + idl].decode()
-        p += idl
-        if "gfx950" in ident:
-            return data[off + eoff: off + eoff + esz]
-    raise SystemExit("no gfx950 entry in bundle")
+    out = []
+    off = data.find(MAGIC)
+    while off >= 0:
+        p = off + len(MAGIC)
+        n, = struct.unpack_from("<Q", data, p)
+        p += 8
+        for _ in range(n):
+            eoff, esz, idl = struct.unpack_from("<QQQ", data, p)
+            p += 24
+            ident = data[p: p + idl].decode()
+            p += idl
+            if "gfx950" in ident:
+                out.append(data[off + eoff: off + eoff + esz])
+        off = data.find(MAGIC, off + len(MAGIC))
+    if not out:
+        raise SystemExit(f"no gfx950 code object in {so_path}")
+    return out
 
 
 def demangle(names):
@@ -42,15 +51,12 @@ def demangle(names):
     return out.stdout.splitlines()
 
 
-def main():
-    so = sys.argv[1] if len(sys.argv) > 1 else os.path.join(
-        os.path.dirname(os.path.abspath(__file__)), "..",
-        "dllama_amd", "ops", "_build", "dllama_hip.so")
-    hsaco = extract_hsaco(so)
-    tmp = "/tmp/_kres.hsaco"
-    open(tmp, "wb").write(hsaco)
-    notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", tmp],
-                           capture_output=True, text=True).stdout
+def kernel_notes(hsaco: bytes) -> list:
+    with tempfile.NamedTemporaryFile(suffix=".hsaco") as f:
+        f.write(hsaco)
+        f.flush()
+        notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", f.name],
+                               capture_output=True, text=True).stdout
     kernels = []
     cur = {}
     for line in notes.splitlines():
@@ -69,11 +75,20 @@ def main():
                 cur[key] = m.group(1) if key == "name" else int(m.group(1))
     if cur:
         kernels.append(cur)
+    return kernels
+
+
+def main():
+    so = sys.argv[1] if len(sys.argv) > 1 else os.path.join(
+        os.path.dirname(os.path.abspath(__file__)), "..",
+        "dllama_amd", "ops", "_build", "dllama_hip.so")
+    kernels = [k for h in extract_hsacos(so) for k in kernel_notes(h)]
     names = demangle([k.get("name", "?") for k in kernels])
     print(f"{'kernel':44s} {'VGPR':>5s} {'AGPR':>5s} {'SGPR':>5s} "
           f"{'LDS':>6s} {'spill':>5s} {'waves/SIMD':>10s}")
     for k, nm in sorted(zip(kernels, names),
-                        key=lambda t: -(t[0].get("vgpr", 0) + t[0].get("agpr", 0))):
+                        key=lambda t: (-(t[0].get("vgpr", 0) + t[0].get("agpr", 0)),
+                                       t[1])):
         short = nm.split("(")[0]
         tot = k.get("vgpr", 0) + k.get("agpr", 0)
         waves = min(8, 512 // max(8, (tot + 7) // 8 * 8)) if tot else 8

@@ -1,6 +1,6 @@
 // Round-2 probe: grouped (MoE expert) Q40 GEMV lane utilization.
 //
-// Production k_q40_gemv_grouped (dllama_kernels.hip) assigns 2 rows/wave
+// Production k_q40_gemv_grouped (dllama_amd/ops/csrc/gemv.hip) assigns 2 rows/wave
 // and strides 16B block-pairs by the FULL 64-lane wave. At Qwen3-30B-A3B
 // shapes that leaves most lanes idle:
 //   w13 per expert: n=2048 -> nbp=32 block-pairs -> lanes 32..63 idle
