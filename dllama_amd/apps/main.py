@@ -89,6 +89,11 @@ def load_engine(args):
             else int(os.environ.get("LOCAL_RANK", "0"))
         model = HipTransformer.from_file(m, cfg, device=f"cuda:{dev}", comm=comm,
                                          n_batches=args.n_batches)
+        # fused temperature/top-p sampler in the captured decode step; read
+        # before the capture, which is what puts it into the graph.
+        # DLLAMA_DEVICE_SAMPLER=0 keeps sampling in Sampler.sample_torch
+        model.device_sampling = \
+            os.environ.get("DLLAMA_DEVICE_SAMPLER", "1") == "1"
         if not args.no_graph:
             # RCCL collectives are hipGraph-capturable, so TP decode is one
             # graph replay per token too (every rank captures in lockstep —

@@ -84,6 +84,34 @@ class InferenceEngine:
         self.pos += 1
         return logits[0]
 
+    def _device_sampling(self) -> bool:
+        """The model samples on device (HipTransformer with device_sampling):
+        it offers sample_row and forward_sample and has not switched them
+        off. Any other model keeps the host sampling path."""
+        m = self.model
+        return (hasattr(m, "sample_row") and hasattr(m, "forward_sample")
+                and bool(getattr(m, "device_sampling", True)))
+
+    @staticmethod
+    def _coin(sampler: Sampler) -> float:
+        """The host Sampler owns the RNG: one draw per sampled token, none at
+        temperature 0 — the same stream as Sampler.sample."""
+        return sampler.next_coin() if sampler.temperature != 0.0 else 0.0
+
+    def decode_sample(self, token: int, sampler: Sampler) -> int:
+        """One decode step with the token sampled on device. When the device
+        sampler gives up (more candidates than its cap) the logits it left in
+        place are resampled on the host path with the same coin."""
+        t = torch.tensor([token], dtype=torch.int64)
+        p = torch.tensor([self.pos], dtype=torch.int64)
+        coin = self._coin(sampler)
+        nxt = self.model.forward_sample(t, p, coin, sampler.temperature,
+                                        sampler.topp)
+        self.pos += 1
+        if nxt is None:
+            nxt = sampler.sample_with_coin(self.model.last_logits(), coin)
+        return nxt
+
     def generate(self, prompt_tokens: list[int], max_tokens: int,
                  on_token=None, stop_check=None) -> tuple[list[int], GenStats]:
         """Greedy/sampled generation. on_token(token_id) is called per new
@@ -100,8 +128,16 @@ class InferenceEngine:
 
         out: list[int] = []
         sampler = self.sampler or Sampler(logits.shape[-1], 0.0, 0.9, 12345)
+        on_device = self._device_sampling()
         t0 = time.perf_counter()
-        token = sampler.sample(logits)
+        if on_device:
+            coin = self._coin(sampler)
+            token = self.model.sample_row(logits, coin, sampler.temperature,
+                                          sampler.topp)
+            if token is None:
+                token = sampler.sample_with_coin(logits, coin)
+        else:
+            token = sampler.sample(logits)
         out.append(token)
         if on_token:
             on_token(token)
@@ -111,8 +147,11 @@ class InferenceEngine:
                 break
             if seq_len is not None and self.pos >= seq_len:
                 break  # context window exhausted (reference clamps via seqLen)
-            logits = self.decode_one(token)
-            token = sampler.sample(logits)
+            if on_device:
+                token = self.decode_sample(token, sampler)
+            else:
+                logits = self.decode_one(token)
+                token = sampler.sample(logits)
             out.append(token)
             if on_token:
                 on_token(token)

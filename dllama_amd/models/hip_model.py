@@ -33,6 +33,7 @@ import torch
 from ..model_file import HIDDEN_ACT_GELU, ModelFile, ROPE_FALCON
 from ..ops import hip_ops
 from ..ops import reference as R
+from ..ops.sampler import DeviceSampler
 from ..parallel.comm import Comm, SingleComm
 from ..quants import Q80, q40_to_planes
 from .config import ModelConfig
@@ -102,6 +103,10 @@ def _pow2_batch(b: int) -> int:
 
 
 class HipTransformer:
+    # opt-in: capture_decode_graph appends the on-device temperature/top-p
+    # sampler to the decode graph (forward_sample); off, nothing changes
+    device_sampling = False
+
     def __init__(self, config: ModelConfig, device=None, comm: Comm | None = None,
                  n_batches: int = 32, force_sync: bool = False):
         self.cfg = c = config
@@ -129,6 +134,8 @@ class HipTransformer:
         self.wcls = None
         self._graph = None
         self._graph_pos = None
+        self._graph_samples = False  # the captured graph ends in the sampler
+        self._dev_sampler = None
         self.greedy_feedback = False
         self.skip_logits = False  # prefill chunks before the last skip wcls
         self._pf_graphs = {}      # skip_logits -> captured 32-token graph
@@ -282,7 +289,13 @@ class HipTransformer:
     def _alloc_buffers(self):
         c, dev, NB = self.cfg, self.device, self.n_batches
         self.pos = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.tokens = torch.zeros(NB, dtype=torch.int64, device=dev)
+        # one allocation for what the host sends per decode step: the token
+        # ids, then the sampler's f64 {coin, temperature, topp, unused}, so
+        # forward_sample stages both with a single small copy
+        self._step_in = torch.zeros(NB + 4, dtype=torch.int64, device=dev)
+        self.tokens = self._step_in[:NB]
+        self.sample_params = self._step_in[NB:].view(torch.float64)
+        self.sample_out = torch.zeros(2, dtype=torch.int64, device=dev)  # token, status
         self.x = torch.zeros(NB, c.dim, device=dev)
         self.t_norm = torch.zeros(NB, c.dim, device=dev)
         self.xq = QuantBuf(NB, c.dim, dev)
@@ -532,7 +545,9 @@ class HipTransformer:
         if not greedy:
             return
         # on-device greedy sampling feeding the next decode step (used by
-        # the fully graph-captured bench loop; real serving samples on host)
+        # the fully graph-captured bench loop; real serving samples after
+        # forward_buffers: the sampler kernels with device_sampling, else
+        # on host)
         if use_amax:
             k.token_from_argmax(self.tokens, self.amax_scratch, self.amax_blocks)
         else:
@@ -767,13 +782,7 @@ class HipTransformer:
                 "(rebuild with a larger --max-seq-len / seq_len)")
         self.tokens[:B].copy_(tokens.to(self.device), non_blocking=True)
         if B == 1 and self._graph is not None:
-            sp = self._pick_splits(p0)
-            if sp != self.attn_splits:
-                self._set_attn_splits(sp)  # recapture at the new K-split count
-            if p0 != self._graph_pos:
-                self.pos.fill_(p0)
-            self._graph.replay()
-            self._graph_pos = p0 + 1  # the graph's pos_inc advanced it
+            self._replay_decode(p0)
         elif B == self.n_batches and not self._pf_failed:
             # full prefill chunks replay a captured graph (eager chunk cost
             # is host-launch-bound: ~400 python kernel launches)
@@ -795,6 +804,76 @@ class HipTransformer:
             self.k.logits_concat(self.logits_full, self.logits_gather[NBp], B)
             return self.logits_full[:B]
         return self.logits0[:B]
+
+    def _replay_decode(self, p0: int):
+        """One replay of the captured decode graph on tokens[0] at p0."""
+        sp = self._pick_splits(p0)
+        if sp != self.attn_splits:
+            self._set_attn_splits(sp)  # recapture at the new K-split count
+        if p0 != self._graph_pos:
+            self.pos.fill_(p0)
+        self._graph.replay()
+        self._graph_pos = p0 + 1  # the graph's pos_inc advanced it
+
+    # ------------------------------------------------------------ sampling
+
+    def last_logits(self) -> torch.Tensor:
+        """The full-vocabulary logits row the last B=1 step left on device.
+        TP: the gathered slices are contiguous in vocabulary order (see
+        _logits), so the flat gather buffer is the row."""
+        if self.tp_path:
+            return self.logits_gather[1].view(-1)[: self.cfg.vocab_size]
+        return self.logits0[0]
+
+    def _sampler(self) -> DeviceSampler:
+        """The sampler's scratch and launches, sharing sample_params and
+        sample_out; built on first use (before a capture: the capture
+        warmups launch the sampler)."""
+        if self._dev_sampler is None:
+            self._dev_sampler = DeviceSampler(
+                self.cfg.vocab_size, self.device, params=self.sample_params,
+                out=self.sample_out, k=self.k)
+            self._step_host = torch.zeros(self.n_batches + 4,
+                                          dtype=torch.int64).pin_memory()
+        return self._dev_sampler
+
+    def sample_row(self, row: torch.Tensor, coin, temperature: float,
+                   topp: float):
+        """Sample from any device f32 logits row, eagerly (first token after
+        prefill, --no-graph). None: resample on the host with the same coin
+        (Sampler.sample_with_coin)."""
+        return self._sampler().sample(row, coin, temperature, topp)
+
+    def forward_sample(self, tokens: torch.Tensor, positions: torch.Tensor,
+                       coin, temperature: float, topp: float):
+        """One decode step and its sampled token: a replay of the decode
+        graph captured with device_sampling (else the step, then the sampler
+        launches). Only the token id and the parameters go to the device and
+        {token, status} comes back; the logits stay in place (last_logits),
+        so a None result can be resampled by the caller."""
+        assert tokens.shape[0] == 1
+        p0 = int(positions[0])
+        if p0 + 1 > self.cfg.seq_len:
+            raise ValueError(
+                f"position {p0}+1 exceeds seq_len {self.cfg.seq_len} "
+                "(rebuild with a larger --max-seq-len / seq_len)")
+        smp, NB = self._sampler(), self.n_batches
+        self._step_host[0] = int(tokens[0])
+        smp.fill_params(self._step_host[NB:].view(torch.float64), coin,
+                        temperature, topp)
+        # one staged copy for token and parameters; tokens[1:] are rewritten
+        # too (zeros): a B=1 step reads tokens[0] only
+        self._step_in.copy_(self._step_host, non_blocking=True)
+        if self._graph is not None:
+            self._replay_decode(p0)
+            if not self._graph_samples:
+                smp.launch(self.last_logits())
+        else:
+            self.pos.fill_(p0)
+            self._graph_pos = None
+            self.forward_buffers(1)
+            smp.launch(self.last_logits())
+        return smp.read()
 
     # ------------------------------------------------------------ graphs
 
@@ -824,21 +903,29 @@ class HipTransformer:
             self._graph_pos = pos_saved
         self._pf_graphs.clear()  # prefill graphs also reference the scratch
 
-    def _warm_and_capture(self, B: int, warmups: int, advance_pos: bool = False):
+    def _warm_and_capture(self, B: int, warmups: int, advance_pos: bool = False,
+                          sample: bool = False):
         """Run forward_buffers(B) `warmups` times on a side stream
         (allocations, lazy kernel loads), then capture it as a hipGraph;
-        advance_pos appends the device position increment."""
+        sample appends the sampler launches over the step's logits row,
+        advance_pos the device position increment."""
+        if sample:
+            self._sampler()  # its buffers exist before anything is captured
         torch.cuda.synchronize(self.device)
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
             for _ in range(warmups):
                 self.forward_buffers(B)
+                if sample:
+                    self._sampler().launch(self.last_logits())
         torch.cuda.current_stream(self.device).wait_stream(s)
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             self.forward_buffers(B)
+            if sample:
+                self._sampler().launch(self.last_logits())
             if advance_pos:
                 self.k.pos_inc(self.pos, 1)
         return g
@@ -861,6 +948,10 @@ class HipTransformer:
         """Capture the whole B=1 decode step (forward + pos advance) as a
         hipGraph; each subsequent decode costs one graph replay
         (the HIP analog of the reference's recorded Vulkan command buffers,
-        nn-vulkan.cpp:1065-1118)."""
-        self._graph = self._warm_and_capture(1, warmups=2, advance_pos=True)
+        nn-vulkan.cpp:1065-1118). With device_sampling the temperature/top-p
+        sampler runs inside it, between the step and the pos advance."""
+        sample = bool(self.device_sampling)
+        self._graph = self._warm_and_capture(1, warmups=2, advance_pos=True,
+                                             sample=sample)
+        self._graph_samples = sample
         self._graph_pos = None  # device pos unknown until first fill

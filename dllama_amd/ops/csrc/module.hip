@@ -9,5 +9,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     register_attn(m);
     register_moe(m);
     register_sync(m);
+    register_sampler(m);
     register_host(m);
 }

@@ -229,3 +229,38 @@ def q80_sync_unpack(buf: torch.Tensor, n: int) -> torch.Tensor:
     q = buf[:, :n].clone().view(torch.int8)
     s = buf[:, n:].contiguous().view(torch.float16).reshape(B, nb)
     return q80_dequantize(q, s.float())
+
+
+# ------------------------------------------------------------ sampling
+
+def sample_ref(logits, temperature: float, topp: float, coin: float):
+    """float64 oracle of the sampler's selection rule (tokenizer.Sampler):
+    returns (token, margin). margin is the smallest relative distance of any
+    decision from flipping — |c_i - topp| over the candidate list and
+    |c_i - r| / c[last] over the nucleus, |cdf_i - coin| in multinomial
+    mode, inf for greedy — so a test can tell which draws are legitimately
+    sensitive to the f32 summation order of an implementation."""
+    import numpy as np
+    if isinstance(logits, torch.Tensor):
+        logits = logits.detach().cpu().numpy()
+    x = np.asarray(logits, dtype=np.float64).reshape(-1)
+    v = x.shape[0]
+    if temperature == 0.0:
+        return int(np.argmax(x)), float("inf")
+    x = x / float(temperature)
+    p = np.exp(x - x.max())
+    p /= p.sum()
+    if topp <= 0 or topp >= 1:
+        cdf = np.cumsum(p)
+        tok = min(int(np.searchsorted(cdf, coin, side="right")), v - 1)
+        return tok, float(np.abs(cdf - coin).min())
+    cutoff = (1.0 - topp) / (v - 1)
+    idx = np.nonzero(p >= cutoff)[0]
+    order = idx[np.argsort(-p[idx], kind="stable")]
+    c = np.cumsum(p[order])
+    last = min(int(np.searchsorted(c, topp, side="right")), len(order) - 1)
+    r = coin * c[last]
+    pick = min(int(np.searchsorted(c[: last + 1], r, side="right")), last)
+    margin = min(float(np.abs(c - topp).min()),
+                 float(np.abs(c[: last + 1] - r).min() / c[last]))
+    return int(order[pick]), margin

@@ -274,16 +274,23 @@ class Sampler:
         u, self.state = _xorshift_u32(self.state)
         return (u >> 8) / 16777216.0
 
-    def sample_torch(self, logits) -> int:
+    def next_coin(self) -> float:
+        """The next xorshift draw in [0, 1): the one random number a sampled
+        token consumes. The host Sampler owns the stream, so TP ranks, the
+        CPU backend and the on-device sampler all see the same coins."""
+        return self._random_f32()
+
+    def sample_torch(self, logits, coin: float | None = None) -> int:
         """Device-side sampling for GPU logits (temperature/softmax/top-p all
         on device; only the chosen token id crosses PCIe). Same xorshift coin
-        as the CPU path."""
+        as the CPU path; drawn here unless the caller passes it."""
         import torch
         logits = logits.reshape(-1)[: self.vocab_size]
         if self.temperature == 0.0:
             return int(torch.argmax(logits).item())
         p = torch.softmax(logits.float() / self.temperature, dim=-1)
-        coin = self._random_f32()
+        if coin is None:
+            coin = self.next_coin()
         if self.topp <= 0 or self.topp >= 1:
             cdf = torch.cumsum(p, dim=-1)
             return int(torch.searchsorted(cdf, torch.tensor(coin, device=p.device),
@@ -305,10 +312,12 @@ class Sampler:
                                       right=True).clamp(0, last).item())
         return int(order[pick].item())
 
-    def sample(self, logits) -> int:
+    def sample_with_coin(self, logits, coin: float | None) -> int:
+        """The selection rule with the coin passed in (ignored, and may be
+        None, at temperature 0)."""
         import torch
         if isinstance(logits, torch.Tensor) and logits.is_cuda:
-            return self.sample_torch(logits)
+            return self.sample_torch(logits, 0.0 if coin is None else coin)
         logits = np.asarray(logits, dtype=np.float32).reshape(-1)[: self.vocab_size]
         if self.temperature == 0.0:
             return int(np.argmax(logits))
@@ -316,7 +325,6 @@ class Sampler:
         x = x - x.max()
         p = np.exp(x)
         p /= p.sum()
-        coin = self._random_f32()
         if self.topp <= 0 or self.topp >= 1:
             cdf = np.cumsum(p)
             return int(np.searchsorted(cdf, coin, side="right").clip(0, self.vocab_size - 1))
@@ -331,6 +339,11 @@ class Sampler:
         r = coin * c[last]
         pick = int(np.searchsorted(c[: last + 1], r, side="right").clip(0, last))
         return int(order[pick])
+
+    def sample(self, logits) -> int:
+        # greedy draws no coin: the stream moves once per sampled token only
+        coin = self.next_coin() if self.temperature != 0.0 else None
+        return self.sample_with_coin(logits, coin)
 
 
 # ---------------------------------------------------------------- chat
