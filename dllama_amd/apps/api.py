@@ -9,15 +9,24 @@ Behavior parity with the reference API server (src/dllama-api.cpp):
     comparison (dllama-api.cpp:298-343)
   - single-slot sequential serving over a stdlib HTTP server (the reference
     hand-rolls HTTP/1.1 the same way, dllama-api.cpp:45-186)
+  - --slots N > 1 (one GPU): a threading server whose handlers enqueue
+    requests to one scheduler thread; it owns the model and a BatchEngine
+    and decodes up to N requests per step. Each request prefills from 0
+    there (no NaiveCache reuse across slots).
 """
 
 from __future__ import annotations
 
 import json
+import queue
 import sys
+import threading
 import time
 import uuid
-from http.server import BaseHTTPRequestHandler, HTTPServer
+from http.server import BaseHTTPRequestHandler, HTTPServer, ThreadingHTTPServer
+
+from ..engine import BatchEngine
+from ..tokenizer import Sampler
 
 from ..tokenizer import (ChatItem, ChatTemplateGenerator, EosDetector,
                          TEMPLATE_UNKNOWN, chat_stops)
@@ -46,9 +55,74 @@ class NaiveCache:
         self.tokens = list(tokens)
 
 
+class BatchScheduler:
+    """The one thread that owns the model in multi-slot serving. Handlers
+    hand it requests over a queue; it admits them into a BatchEngine between
+    steps, and every request's tokens flow back through the callbacks the
+    request was submitted with (called on this thread)."""
+
+    def __init__(self, model, tokenizer, n_batches: int):
+        self.engine = BatchEngine(model, tokenizer, n_batches)
+        self.inbox: queue.Queue = queue.Queue()
+        self.active = []  # (sequence, on_done)
+        self.thread = threading.Thread(target=self._loop, daemon=True)
+        self.thread.start()
+
+    def submit(self, tokens, max_tokens, sampler, on_token, stop_check, on_done):
+        """on_done(error_or_None) is called once, after the last on_token."""
+        self.inbox.put((tokens, max_tokens, sampler, on_token, stop_check,
+                        on_done))
+
+    def stop(self):
+        self.inbox.put(None)
+        self.thread.join()
+
+    def _admit(self, item):
+        *request, on_done = item
+        try:
+            self.active.append((self.engine.submit(*request), on_done))
+        except Exception as e:  # noqa: BLE001  (e.g. prompt beyond seq_len)
+            on_done(e)
+
+    def _loop(self):
+        while True:
+            # block while there is nothing to step, else just drain
+            try:
+                item = self.inbox.get(block=self.engine.idle)
+                if item is None:
+                    return
+                self._admit(item)
+                continue
+            except queue.Empty:
+                pass
+            try:
+                self.engine.step()
+                error = None
+            except Exception as e:  # noqa: BLE001
+                error = e
+            still = []
+            for seq, on_done in self.active:
+                if error is not None or seq.done:
+                    on_done(error)
+                else:
+                    still.append((seq, on_done))
+            self.active = still
+            if error is not None:
+                # the engine's bookkeeping is no longer trustworthy
+                m, tok = self.engine.model, self.engine.tokenizer
+                self.engine = BatchEngine(m, tok, self.engine.n_batches)
+
+
 class ApiState:
     def __init__(self, args):
         self.engine, self.m, self.comm = load_engine(args)
+        # --slots > 1: requests decode together (load_engine has refused it
+        # under tensor parallelism)
+        self.scheduler = None
+        if getattr(args, "slots", 1) > 1:
+            self.scheduler = BatchScheduler(self.engine.model,
+                                            self.engine.tokenizer,
+                                            self.engine.n_batches)
         self.tok = self.engine.tokenizer
         eos_piece = (self.tok.vocab[self.tok.eos_token_ids[0]]
                      .decode("utf-8", "replace") if self.tok.eos_token_ids else "")
@@ -68,6 +142,8 @@ class ApiState:
                  for m in body.get("messages", [])]
         text = self.template.generate(items, True).content
         tokens = self.tok.encode(text)
+        if self.scheduler is not None:
+            return self._complete_batched(body, tokens, emit)
         start = self.cache.resolve(tokens)
         self.engine.reset(start)
         max_tokens = int(body.get("max_tokens") or 256)
@@ -109,6 +185,51 @@ class ApiState:
         # the evaluated endPos, dllama-api.cpp:470-473)
         self.cache.update(tokens + gen_tokens[:-1])
         return "".join(out_text), len(tokens), len(gen_tokens)
+
+
+    def _complete_batched(self, body: dict, tokens: list, emit):
+        """complete() in multi-slot mode: the request gets its own sampler,
+        detector and streaming decoder, runs on the scheduler thread next to
+        the other requests, and its deltas come back over a queue."""
+        def param(name, default, cast):
+            return cast(body[name]) if body.get(name) is not None else default
+
+        sampler = Sampler(self.m.header.vocab_size,
+                          param("temperature", self.default_temp, float),
+                          param("top_p", self.default_topp, float),
+                          param("seed", self.default_seed, int))
+        user_stop = body.get("stop") or []
+        if isinstance(user_stop, str):
+            user_stop = [user_stop]
+        detector = EosDetector(self.tok.eos_token_ids,
+                               chat_stops(self.tok) + user_stop)
+        tok = self.tok.fork_decoder()
+        deltas: queue.Queue = queue.Queue()
+        generated = [0]
+
+        def on_token(t):
+            generated[0] += 1
+            kind = detector.append(t, tok.decode(t))
+            if kind != 0:  # not MAYBE_EOS
+                delta = detector.get_delta()
+                if delta:
+                    deltas.put(delta)
+                    detector.reset()
+
+        self.scheduler.submit(
+            tokens, int(body.get("max_tokens") or 256), sampler, on_token,
+            lambda t: detector.is_eos(t) or detector.eos_pos >= 0,
+            lambda error: deltas.put(error if error is not None else StopIteration))
+        out_text = []
+        while True:
+            item = deltas.get()
+            if item is StopIteration:
+                break
+            if isinstance(item, Exception):
+                raise item
+            out_text.append(item)
+            emit(item)
+        return "".join(out_text), len(tokens), generated[0]
 
 
 STATE: ApiState | None = None
@@ -213,7 +334,9 @@ def main(argv=None) -> int:
             follower_loop(STATE.engine.model, comm)
             return 0
         STATE.engine.model = RootModel(STATE.engine.model, comm)
-    server = HTTPServer((args.host, args.port), Handler)
+    multi = STATE.scheduler is not None
+    server = (ThreadingHTTPServer if multi else HTTPServer)(
+        (args.host, args.port), Handler)
     print(f"⭐ dllama-api listening on {args.host}:{args.port}")
     try:
         server.serve_forever()
@@ -222,6 +345,8 @@ def main(argv=None) -> int:
     finally:
         if comm.world > 1 and comm.rank == 0:
             STATE.engine.model.stop_followers()
+        if multi:
+            STATE.scheduler.stop()
     return 0
 
 

@@ -37,6 +37,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--model", required=False)
     p.add_argument("--tokenizer", required=False)
     p.add_argument("--prompt", default=None)
+    p.add_argument("--prompt-file", default=None,
+                   help="inference: one prompt per line, generated together "
+                        "in --slots KV slots; completions print in input "
+                        "order, each prefixed with its index")
+    p.add_argument("--slots", type=int, default=1,
+                   help="KV slots = sequences decoded per step (--prompt-file, "
+                        "dllama-api); 1 is the single-sequence path")
     p.add_argument("--steps", type=int, default=64)
     p.add_argument("--buffer-float-type", default="q80", choices=["q80", "f32"],
                    help="TP sync buffer quantization (reference --buffer-float-type)")
@@ -77,24 +84,37 @@ def build_parser() -> argparse.ArgumentParser:
 def load_engine(args):
     """Model + tokenizer + engine with the right backend and TP setup."""
     comm = init_dist_comm()
+    slots = getattr(args, "slots", 1)
+    if slots < 1:
+        raise SystemExit("error: --slots must be >= 1")
+    if slots > 1 and comm.world > 1:
+        # the lockstep control packet carries a single position
+        raise SystemExit(
+            f"error: --slots {slots} needs a single GPU (world is "
+            f"{comm.world}): multi-slot serving under tensor parallelism is "
+            "not supported yet")
     sync = Q80 if args.buffer_float_type == "q80" else F32
     m = mf.ModelFile(args.model, max_seq_len=args.max_seq_len, sync_type=sync)
     use_gpu = torch.cuda.is_available() and args.gpu_index != -1
     cfg = ModelConfig.from_header(m.header, world=comm.world, rank=comm.rank)
     if comm.rank == 0:
-        _print_header(m.header, cfg, use_gpu)
+        _print_header(m.header, cfg, use_gpu, slots)
     if use_gpu:
         from ..models.hip_model import HipTransformer
         dev = args.gpu_index if args.gpu_index is not None \
             else int(os.environ.get("LOCAL_RANK", "0"))
         model = HipTransformer.from_file(m, cfg, device=f"cuda:{dev}", comm=comm,
-                                         n_batches=args.n_batches)
+                                         n_batches=args.n_batches,
+                                         n_slots=slots)
         # fused temperature/top-p sampler in the captured decode step; read
         # before the capture, which is what puts it into the graph.
         # DLLAMA_DEVICE_SAMPLER=0 keeps sampling in Sampler.sample_torch
         model.device_sampling = \
             os.environ.get("DLLAMA_DEVICE_SAMPLER", "1") == "1"
-        if not args.no_graph:
+        # several slots step through forward_rows, which captures its own
+        # all-decode graphs lazily: the single-sequence graph is not needed
+        model.row_graphs = not args.no_graph
+        if not args.no_graph and slots == 1:
             # RCCL collectives are hipGraph-capturable, so TP decode is one
             # graph replay per token too (every rank captures in lockstep —
             # the warmup forwards inside contain collectives)
@@ -109,7 +129,8 @@ def load_engine(args):
         torch.set_num_threads(max(1, args.nthreads))
         wdt = ("q40" if args.cpu_dtype == "q40"
                else torch.float16 if args.cpu_dtype == "f16" else torch.float32)
-        model = CpuTransformer(m, cfg, comm, weight_dtype=wdt)
+        model = CpuTransformer(m, cfg, comm, weight_dtype=wdt, n_slots=slots,
+                               n_batches=args.n_batches)
     tok = Tokenizer(args.tokenizer) if args.tokenizer else None
     seed = args.seed if args.seed is not None else int(time.time())
     if comm.world > 1:
@@ -124,7 +145,7 @@ def load_engine(args):
     return InferenceEngine(model, tok, sampler, n_batches=nb), m, comm
 
 
-def _print_header(h, cfg, use_gpu):
+def _print_header(h, cfg, use_gpu, slots=1):
     print(f"💡 Arch: {'Llama' if h.arch_type == mf.ARCH_LLAMA else 'Qwen3 MoE' if h.arch_type == mf.ARCH_QWEN3_MOE else 'Qwen3'}")
     print(f"💡 Dim: {h.dim}\n💡 HiddenDim: {h.hidden_dim}\n💡 nLayers: {h.n_layers}")
     print(f"💡 nHeads: {h.n_heads}\n💡 nKvHeads: {h.n_kv_heads}\n💡 HeadDim: {h.head_dim}")
@@ -134,14 +155,17 @@ def _print_header(h, cfg, use_gpu):
     print(f"💡 Backend: {'MI355X HIP' if use_gpu else 'CPU'}  TP={cfg.world}")
     # memory accounting (reference 📀 prints, nn-core.cpp:175-189): per-rank
     # resident weight shard + dense f32 KV cache
-    kv_bytes = 2 * cfg.n_layers * cfg.seq_len * cfg.kv_dim0 * 4
+    kv_bytes = 2 * cfg.n_layers * cfg.seq_len * cfg.kv_dim0 * 4 * slots
     weights = h.file_size - h.header_size  # .m = header + packed weights
     print(f"📀 Weights/rank: {weights / max(1, cfg.world) / 1e9:.2f} GB"
-          f"  KV cache/rank: {kv_bytes / 1e9:.2f} GB (seq {cfg.seq_len})")
+          f"  KV cache/rank: {kv_bytes / 1e9:.2f} GB (seq {cfg.seq_len}"
+          + (f" x {slots} slots)" if slots > 1 else ")"))
 
 
 def run_inference(args) -> int:
     engine, m, comm = load_engine(args)
+    if args.prompt_file is not None:
+        return run_inference_many(args, engine)
     if args.prompt is None:
         print("error: missing --prompt", file=sys.stderr)
         return 1
@@ -180,6 +204,52 @@ def run_inference(args) -> int:
               f"   tokens/s: {stats.eval_tok_s:.2f} ({1000.0 / max(stats.eval_tok_s, 1e-9):.2f} ms/tok)")
         print(f"Prediction\n   nTokens: {stats.decode_tokens}\n"
               f"   tokens/s: {stats.pred_tok_s:.2f} ({1000.0 / max(stats.pred_tok_s, 1e-9):.2f} ms/tok)")
+    return 0
+
+
+def run_inference_many(args, engine) -> int:
+    """--prompt-file: every line a prompt, generated together through a
+    BatchEngine over the model's KV slots. Completions print in input order
+    once all are done, then the stats block with aggregate tokens/s."""
+    from ..engine import BatchEngine
+    with open(args.prompt_file, encoding="utf-8") as f:
+        prompts = [line.rstrip("\n") for line in f if line.strip()]
+    if not prompts:
+        print("error: no prompt in --prompt-file", file=sys.stderr)
+        return 1
+    tok = engine.tokenizer
+    encoded = [tok.encode(p) if tok else [int(t) for t in p.split()]
+               for p in prompts]
+    base = engine.sampler
+    # one RNG stream per sequence: what a prompt generates does not depend
+    # on what it is batched with
+    samplers = [Sampler(base.vocab_size, base.temperature, base.topp,
+                        base.state + i) for i in range(len(prompts))]
+    batch = BatchEngine(engine.model, tok, n_batches=engine.n_batches)
+    stop = (lambda i, t: tok.is_eos(t)) if tok else None
+    engine._sync_device()
+    t0 = time.perf_counter()
+    results = batch.generate_many(encoded, args.steps, samplers=samplers,
+                                  stop_check=stop)
+    engine._sync_device()
+    wall = time.perf_counter() - t0
+    for i, (prompt, (out, _)) in enumerate(zip(prompts, results)):
+        if tok:
+            tok.reset_decoder()
+            text = "".join(tok.decode(t) or "" for t in out)
+        else:
+            text = " " + " ".join(str(t) for t in out)
+        print(f"[{i}] {prompt}{text}")
+    n_eval = sum(st.prefill_tokens for _, st in results)
+    n_pred = sum(st.decode_tokens for _, st in results)
+    eval_s = n_eval / max(sum(st.prefill_time for _, st in results), 1e-9)
+    pred_s = n_pred / max(wall, 1e-9)
+    print(f"Evaluation\n   nBatches: {args.n_batches}\n   nTokens: {n_eval}\n"
+          f"   tokens/s: {eval_s:.2f} ({1000.0 / max(eval_s, 1e-9):.2f} ms/tok)")
+    print(f"Prediction\n   nSequences: {len(prompts)} in {args.slots} slots\n"
+          f"   nTokens: {n_pred}\n"
+          f"   tokens/s: {pred_s:.2f} aggregate "
+          f"({1000.0 / max(pred_s, 1e-9):.2f} ms/tok)")
     return 0
 
 

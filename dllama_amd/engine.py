@@ -9,6 +9,10 @@ Under TP every rank runs the engine in lockstep; logits are gathered on all
 ranks and sampling is deterministic (same seed), so no extra token
 broadcast is needed (replaces the reference LlmControlPacket root->worker
 broadcast, app.cpp:197-230).
+
+BatchEngine (beyond the reference, which serves one sequence) steps many
+sequences together through a model's KV slots, one ragged forward_rows step
+at a time; InferenceEngine stays the single-sequence path.
 """
 
 from __future__ import annotations
@@ -159,6 +163,190 @@ class InferenceEngine:
         stats.decode_time = time.perf_counter() - t0
         stats.decode_tokens = len(out)
         return out, stats
+
+
+class _Sequence:
+    """One submitted request of a BatchEngine."""
+
+    def __init__(self, prompt, max_tokens, sampler, on_token, stop_check):
+        self.prompt = list(prompt)
+        self.max_tokens = max_tokens
+        self.sampler = sampler
+        self.on_token = on_token
+        self.stop_check = stop_check
+        self.slot = None      # KV slot while running
+        self.fed = 0          # prompt tokens already stepped
+        self.out: list[int] = []
+        self.done = False
+        self.stats = GenStats(prefill_tokens=len(self.prompt))
+        self._t0 = None       # when first scheduled, then when first sampled
+
+    @property
+    def tokens(self) -> list[int]:
+        return self.out
+
+    @property
+    def prefilling(self) -> bool:
+        return self.fed < len(self.prompt)
+
+
+class BatchEngine:
+    """Many sequences through one model, one ragged step at a time.
+
+    The model (HipTransformer or CpuTransformer, built with n_slots slots)
+    offers forward_rows; every running sequence owns one of its KV slots.
+    step() builds one step of at most n_batches rows: first one decode row
+    for every running sequence, then prompt chunks of the sequences that are
+    still prefilling, in submission order. Sequences beyond the slot count
+    wait; a finished sequence frees its slot for the next. Each sequence
+    owns its Sampler (its own RNG stream), so what it generates does not
+    depend on what it is batched with."""
+
+    def __init__(self, model, tokenizer=None, n_batches: int = 32):
+        if not hasattr(model, "forward_rows"):
+            raise ValueError("BatchEngine needs a model with forward_rows")
+        self.model = model
+        self.tokenizer = tokenizer
+        self.n_batches = min(n_batches, getattr(model, "n_batches", n_batches))
+        self.seq_len = model.cfg.seq_len
+        self.free_slots = list(range(model.n_slots))
+        self.waiting: list[_Sequence] = []
+        self.running: list[_Sequence] = []
+        self.last_step_rows: list[tuple] = []  # (sequence, position) per row
+
+    _coin = staticmethod(InferenceEngine._coin)
+
+    def _on_device(self) -> bool:
+        """The model samples rows on device (HipTransformer with
+        device_sampling); any other model samples on the host."""
+        return (hasattr(self.model, "forward_rows_sample")
+                and bool(getattr(self.model, "device_sampling", False)))
+
+    def submit(self, prompt_tokens: list[int], max_tokens: int,
+               sampler: Sampler | None = None, on_token=None,
+               stop_check=None) -> _Sequence:
+        """Queue a request; the handle's .tokens grows as it generates and
+        .done turns True when it ended (max_tokens, stop_check or the end
+        of the context window), .stats holding its timing."""
+        if len(prompt_tokens) < 1:
+            raise ValueError("empty prompt")
+        if len(prompt_tokens) > self.seq_len:
+            raise ValueError(
+                f"prompt of {len(prompt_tokens)} tokens exceeds seq_len "
+                f"{self.seq_len} (rebuild with a larger --max-seq-len / seq_len)")
+        if sampler is None:
+            sampler = Sampler(self.model.cfg.vocab_size, 0.0, 0.9, 12345)
+        seq = _Sequence(prompt_tokens, max_tokens, sampler, on_token,
+                        stop_check)
+        self.waiting.append(seq)
+        return seq
+
+    @property
+    def idle(self) -> bool:
+        return not self.waiting and not self.running
+
+    def _plan(self):
+        """Rows of the next step as (sequence, token, position, samples)."""
+        while self.waiting and self.free_slots:
+            seq = self.waiting.pop(0)
+            seq.slot = self.free_slots.pop(0)
+            self.running.append(seq)
+        rows = []
+        for seq in self.running:
+            if not seq.prefilling:
+                pos = len(seq.prompt) + len(seq.out) - 1
+                rows.append((seq, seq.out[-1], pos, True))
+        for seq in self.running:
+            room = self.n_batches - len(rows)
+            if room <= 0:
+                break
+            if seq.prefilling:
+                chunk = seq.prompt[seq.fed: seq.fed + room]
+                last = seq.fed + len(chunk) == len(seq.prompt)
+                for i, tok in enumerate(chunk):
+                    rows.append((seq, tok, seq.fed + i,
+                                 last and i == len(chunk) - 1))
+        return rows
+
+    def step(self) -> None:
+        """Run one ragged step and hand every sampled token to its
+        sequence."""
+        rows = self._plan()
+        if not rows:
+            return
+        now = time.perf_counter()
+        for seq, _, _, _ in rows:
+            if seq._t0 is None:
+                seq._t0 = now
+        self.last_step_rows = [(seq, pos) for seq, _, pos, _ in rows]
+        tokens = [tok for _, tok, _, _ in rows]
+        slots = [seq.slot for seq, _, _, _ in rows]
+        positions = [pos for _, _, pos, _ in rows]
+        model = self.model
+        if self._on_device():
+            coins = [self._coin(seq.sampler) if smp else 0.0
+                     for seq, _, _, smp in rows]
+            temps = [seq.sampler.temperature if smp else 0.0
+                     for seq, _, _, smp in rows]
+            topps = [seq.sampler.topp for seq, _, _, _ in rows]
+            picked = model.forward_rows_sample(tokens, slots, positions, coins,
+                                               temps, topps)
+            logits = None
+            for b, (seq, _, _, smp) in enumerate(rows):
+                if smp and picked[b] is None:
+                    if logits is None:
+                        logits = model.rows_logits(len(rows))
+                    picked[b] = seq.sampler.sample_with_coin(logits[b], coins[b])
+        else:
+            logits = model.forward_rows(tokens, slots, positions)
+            picked = [seq.sampler.sample(logits[b]) if smp else None
+                      for b, (seq, _, _, smp) in enumerate(rows)]
+        now = time.perf_counter()
+        for b, (seq, _, pos, smp) in enumerate(rows):
+            if seq.prefilling:
+                seq.fed += 1
+            if smp:
+                self._accept(seq, int(picked[b]), now)
+
+    def _accept(self, seq: _Sequence, token: int, now: float) -> None:
+        if not seq.out:
+            seq.stats.prefill_time = now - seq._t0
+            seq._t0 = now  # decode time runs from the first token on
+        seq.out.append(token)
+        if seq.on_token:
+            seq.on_token(token)
+        # the same three ends as InferenceEngine.generate, in its order
+        next_pos = len(seq.prompt) + len(seq.out) - 1
+        if (len(seq.out) >= seq.max_tokens
+                or (seq.stop_check and seq.stop_check(token))
+                or next_pos >= self.seq_len):
+            seq.done = True
+            seq.stats.decode_tokens = len(seq.out)
+            seq.stats.decode_time = now - seq._t0
+            self.running.remove(seq)
+            self.free_slots.append(seq.slot)
+            self.free_slots.sort()
+            seq.slot = None
+
+    def run(self) -> None:
+        """Step until every submitted sequence has ended."""
+        while not self.idle:
+            self.step()
+
+    def generate_many(self, prompts: list[list[int]], max_tokens: int,
+                      samplers: list | None = None, on_token=None,
+                      stop_check=None) -> list[tuple[list[int], GenStats]]:
+        """Generate for every prompt; results in input order. samplers: one
+        Sampler per prompt (default greedy); on_token(index, token) and
+        stop_check(index, token) get the prompt's index first."""
+        seqs = []
+        for i, prompt in enumerate(prompts):
+            seqs.append(self.submit(
+                prompt, max_tokens, samplers[i] if samplers else None,
+                (lambda t, i=i: on_token(i, t)) if on_token else None,
+                (lambda t, i=i: stop_check(i, t)) if stop_check else None))
+        self.run()
+        return [(s.out, s.stats) for s in seqs]
 
 
 def _to_numpy(x: torch.Tensor):

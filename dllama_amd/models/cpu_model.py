@@ -41,8 +41,15 @@ class Q40W:
 
 class CpuTransformer:
     def __init__(self, m: ModelFile, config: ModelConfig, comm: Comm | None = None,
-                 activation_quant: bool = True, weight_dtype: torch.dtype = torch.float32):
+                 activation_quant: bool = True, weight_dtype: torch.dtype = torch.float32,
+                 n_slots: int = 1, n_batches: int = 32):
         self.cfg = config
+        if n_slots < 1:
+            raise ValueError(f"n_slots must be >= 1 (got {n_slots})")
+        # KV slots: n_slots sequences of seq_len cache rows each; forward
+        # lives in slot 0, forward_rows addresses any of them
+        self.n_slots = n_slots
+        self.n_batches = n_batches  # most rows forward_rows takes per step
         self.comm = comm or SingleComm()
         self.activation_quant = activation_quant  # False = pure f32 (debugging)
         self.skip_logits = False  # accepted for engine compat; CPU always computes
@@ -101,8 +108,8 @@ class CpuTransformer:
             self.layers.append(lw)
 
         self.rope = R.rope_cache(c.seq_len, c.head_dim, c.rope_theta, c.rope_scaling)
-        self.k_cache = torch.zeros(c.n_layers, c.seq_len, c.kv_dim0)
-        self.v_cache = torch.zeros(c.n_layers, c.seq_len, c.kv_dim0)
+        self.k_cache = torch.zeros(c.n_layers, n_slots * c.seq_len, c.kv_dim0)
+        self.v_cache = torch.zeros(c.n_layers, n_slots * c.seq_len, c.kv_dim0)
 
     # ------------------------------------------------------------------
 
@@ -133,11 +140,35 @@ class CpuTransformer:
 
     def forward(self, tokens: torch.Tensor, positions: torch.Tensor) -> torch.Tensor:
         """tokens, positions: int64 [B] -> logits f32 [B, vocab] (all ranks)."""
+        if int(positions[-1]) >= self.cfg.seq_len:
+            raise ValueError(
+                f"position {int(positions[-1])} exceeds seq_len "
+                f"{self.cfg.seq_len}")
+        return self._step(tokens, positions, None)
+
+    def forward_rows(self, tokens, slots, positions) -> torch.Tensor:
+        """One ragged step: row b feeds tokens[b] at positions[b] of the
+        sequence in KV slot slots[b] -> logits f32 [B, vocab]. Decode rows
+        of different sequences, prompt chunks, or both; rows of one slot see
+        each other's K/V. ValueError for a slot >= n_slots, a position >=
+        seq_len, a repeated (slot, position) or more than n_batches rows."""
+        from .rows import check_rows
+        c = self.cfg
+        tokens, slots, positions = check_rows(
+            tokens, slots, positions, self.n_slots, c.seq_len, self.n_batches)
+        return self._step(torch.tensor(tokens, dtype=torch.int64),
+                          torch.tensor(positions, dtype=torch.int64),
+                          [s * c.seq_len for s in slots])
+
+    def _step(self, tokens: torch.Tensor, positions: torch.Tensor,
+              bases: list | None) -> torch.Tensor:
+        """The layer stream over B rows. bases: every row's first cache row
+        (slot * seq_len); None = all rows in slot 0."""
         c = self.cfg
         B = tokens.shape[0]
-        if int(positions[-1]) >= c.seq_len:
-            raise ValueError(
-                f"position {int(positions[-1])} exceeds seq_len {c.seq_len}")
+        cache_rows = positions.long()
+        if bases is not None:
+            cache_rows = cache_rows + torch.tensor(bases, dtype=torch.int64)
         x = self.embedding[tokens.long()].clone()  # [B, dim], replicated
 
         for l, lw in enumerate(self.layers):
@@ -152,10 +183,19 @@ class CpuTransformer:
                                c.norm_eps).reshape(B, -1)
             q = self._rope(q, positions)
             k = self._rope(k, positions)
-            self.k_cache[l, positions.long()] = k
-            self.v_cache[l, positions.long()] = v
-            z = R.attention(q, self.k_cache[l], self.v_cache[l], positions,
-                            c.n_heads0, c.head_dim)
+            self.k_cache[l, cache_rows] = k
+            self.v_cache[l, cache_rows] = v
+            if bases is None:
+                z = R.attention(q, self.k_cache[l], self.v_cache[l], positions,
+                                c.n_heads0, c.head_dim)
+            else:
+                # every row attends inside its own slot's cache slice
+                z = torch.cat([
+                    R.attention(q[b:b + 1],
+                                self.k_cache[l, base: base + c.seq_len],
+                                self.v_cache[l, base: base + c.seq_len],
+                                positions[b:b + 1], c.n_heads0, c.head_dim)
+                    for b, base in enumerate(bases)])
             partial = self._matmul(z, lw["wo"])
             x = x + self._sync(partial)
 

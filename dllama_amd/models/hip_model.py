@@ -21,6 +21,12 @@ once): `forward_buffers` (explicit norm_quant per matmul; any batch),
 producers' epilogues) and `_forward_prefill_bf16` (library bf16 GEMMs, an
 A/B baseline). tests/test_launch_trace.py pins the resulting launch
 sequences.
+
+A fourth schedule, `_forward_rows_buffers`, steps rows of several sequences
+together: the KV cache holds `n_slots` sequences and a per-row {cache row
+base, position} table replaces "row b is position pos+b" in rope, KV write
+and attention (`forward_rows`, docs/DESIGN.md §8). With the default of one
+slot nothing of it is allocated or launched.
 """
 
 from __future__ import annotations
@@ -108,8 +114,15 @@ class HipTransformer:
     device_sampling = False
 
     def __init__(self, config: ModelConfig, device=None, comm: Comm | None = None,
-                 n_batches: int = 32, force_sync: bool = False):
+                 n_batches: int = 32, force_sync: bool = False,
+                 n_slots: int = 1):
         self.cfg = c = config
+        # KV slots: each layer's cache holds n_slots sequences of seq_len
+        # rows; every single-sequence path lives in slot 0 (the first
+        # seq_len rows), forward_rows addresses any of them
+        if n_slots < 1:
+            raise ValueError(f"n_slots must be >= 1 (got {n_slots})")
+        self.n_slots = n_slots
         self.comm = comm or SingleComm()
         # force_sync: run the full TP sync/gather/concat path at world=1
         # (SingleComm collectives are identity) — lets a 1-GPU box validate
@@ -140,6 +153,10 @@ class HipTransformer:
         self.skip_logits = False  # prefill chunks before the last skip wcls
         self._pf_graphs = {}      # skip_logits -> captured 32-token graph
         self._pf_failed = False
+        self.row_graphs = True    # capture all-decode forward_rows steps
+        self._row_graphs = {}     # B -> captured all-decode row step
+        self._row_graphs_failed = False
+        self._rows_io = None      # row-step staging, built on first use
         # per-model constants
         self.kv_mul = c.n_heads0 // max(1, c.kv_dim0 // c.head_dim)
         self.rope_style = 1 if c.rope_type == ROPE_FALCON else 0
@@ -195,14 +212,15 @@ class HipTransformer:
     @classmethod
     def from_file(cls, m: ModelFile, config: ModelConfig, device=None,
                   comm: Comm | None = None, n_batches: int = 32,
-                  force_sync: bool = False) -> "HipTransformer":
+                  force_sync: bool = False,
+                  n_slots: int = 1) -> "HipTransformer":
         from ..quants import Q40
         if m.header.weight_type != Q40:
             raise ValueError(
                 "the MI355X HIP backend runs Q40 weights (the reference's "
                 "shipped format); f32/q80 .m files run on the CPU backend "
                 "(--gpu-index -1) or can be re-quantized with convert_hf.py")
-        self = cls(config, device, comm, n_batches, force_sync)
+        self = cls(config, device, comm, n_batches, force_sync, n_slots)
         c, dev = config, self.device
         r, w = c.rank, c.world
 
@@ -252,10 +270,11 @@ class HipTransformer:
     @classmethod
     def synthetic(cls, config: ModelConfig, device=None, comm: Comm | None = None,
                   n_batches: int = 32, seed: int = 1234,
-                  force_sync: bool = False) -> "HipTransformer":
+                  force_sync: bool = False,
+                  n_slots: int = 1) -> "HipTransformer":
         """Random-init weights built directly on device (benches: no network
         for checkpoints, and an 8B .m file round-trip is pointless there)."""
-        self = cls(config, device, comm, n_batches, force_sync)
+        self = cls(config, device, comm, n_batches, force_sync, n_slots)
         c, dev = config, self.device
         gen = torch.Generator(device=dev)
         gen.manual_seed(seed + c.rank)
@@ -383,9 +402,10 @@ class HipTransformer:
         cache = R.rope_cache(c.seq_len, c.head_dim, c.rope_theta, c.rope_scaling)
         self.rope_cache = cache.reshape(c.seq_len, c.head_dim).contiguous().to(dev)
         kv_dt = torch.float32 if self.kv_f32 else torch.float16
-        self.k_cache = [torch.zeros(c.seq_len, c.kv_dim0, dtype=kv_dt, device=dev)
+        kv_rows = self.n_slots * c.seq_len  # slot s = rows s*seq_len ...
+        self.k_cache = [torch.zeros(kv_rows, c.kv_dim0, dtype=kv_dt, device=dev)
                         for _ in range(c.n_layers)]
-        self.v_cache = [torch.zeros(c.seq_len, c.kv_dim0, dtype=kv_dt, device=dev)
+        self.v_cache = [torch.zeros(kv_rows, c.kv_dim0, dtype=kv_dt, device=dev)
                         for _ in range(c.n_layers)]
 
     # ------------------------------------------------------------ stages
@@ -440,6 +460,35 @@ class HipTransformer:
         k.rope_kv(self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0,
                   self.rope_cache, self.pos, self.k_cache[l], self.v_cache[l],
                   c.head_dim, self.rope_style, B)
+
+    def _rope_kv_rows(self, l: int, lw: dict, B: int):
+        """_qknorm_rope_kv with every row's rope position and cache row
+        taken from the row table."""
+        c, k = self.cfg, self.k
+        if c.is_qwen3 and self.rope_style == 1:
+            k.rope_kv_qknorm_rows(self.qkv_out, self.qkv_ld, c.q_dim0,
+                                  c.kv_dim0, self.rope_cache, self.rows,
+                                  self.k_cache[l], self.v_cache[l], c.head_dim,
+                                  lw["q_norm"], lw["k_norm"], c.norm_eps, B)
+            return
+        if c.is_qwen3:
+            for col0, width, wn in ((0, c.q_dim0, lw["q_norm"]),
+                                    (c.q_dim0, c.kv_dim0, lw["k_norm"])):
+                k.rmsnorm_rows_s(self.qkv_out, self.qkv_ld, col0,
+                                 width // c.head_dim, B, wn, c.head_dim,
+                                 c.norm_eps)
+        k.rope_kv_rows(self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0,
+                       self.rope_cache, self.rows, self.k_cache[l],
+                       self.v_cache[l], c.head_dim, self.rope_style, B)
+
+    def _attn_rows(self, l: int, B: int):
+        """Attention of every row over its own slot's rows of layer l's
+        cache, into the Q80 triple zq that the wo matmul consumes."""
+        c = self.cfg
+        self.k.attn_rows(self.qkv_out, self.qkv_ld, self.k_cache[l],
+                         self.v_cache[l], self.zbuf[:B], self.rows, B,
+                         c.n_heads0, self.kv_mul, c.head_dim, self.attn_splits,
+                         self.attn_ml, self.attn_o, *self.zq.triple())
 
     def _attn(self, l: int, B: int, emit_q80: bool = True):
         """Attention over layer l's cache into zbuf[:B]; emit_q80 also
@@ -526,11 +575,13 @@ class HipTransformer:
             k.q40_gemv_resid_q(lin.qs, lin.scales, *qb.triple(), self.x, ssq,
                                wnorm, *self.xq.triple())
 
-    def _logits(self, B: int, NB: int, slot: int, deferred: bool = False):
+    def _logits(self, B: int, NB: int, slot: int, deferred: bool = False,
+                feedback: bool = True):
         """wcls matmul over the final norm, TP gather of the vocab shards,
-        and (greedy_feedback, B=1) the on-device argmax into tokens[0]."""
+        and (greedy_feedback, B=1) the on-device argmax into tokens[0];
+        feedback=False leaves tokens alone whatever greedy_feedback says."""
         c, k = self.cfg, self.k
-        greedy = self.greedy_feedback and B == 1
+        greedy = self.greedy_feedback and B == 1 and feedback
         use_amax = greedy and not self.tp_path
         amax = self.amax_scratch if use_amax else None
         if deferred:
@@ -875,6 +926,189 @@ class HipTransformer:
             smp.launch(self.last_logits())
         return smp.read()
 
+    # ------------------------------------------------------------ row steps
+
+    def _rows_buffers(self):
+        """What the host sends per ragged step, in one allocation so a
+        single small copy stages it: int64 words [tokens NB | per-row sampler
+        f64 {coin, temperature, topp, unused} 4*NB | row table int32 [NB, 2]].
+        The table is last: a step whose table the device already holds (a
+        replayed graph advanced it) copies the prefix only. Built on first
+        use, with its pinned host twin."""
+        if self._rows_io is None:
+            NB, dev = self.n_batches, self.device
+            self._rows_io = io = torch.zeros(6 * NB, dtype=torch.int64, device=dev)
+            self.row_tokens = io[:NB]
+            self.row_params = io[NB:5 * NB].view(torch.float64).view(NB, 4)
+            self.rows = io[5 * NB:].view(torch.int32).view(NB, 2)
+            self.rows_sample_out = torch.zeros(NB, 2, dtype=torch.int64,
+                                               device=dev)  # token, status
+            self._rows_host = torch.zeros(6 * NB, dtype=torch.int64)
+            if dev.type == "cuda":
+                self._rows_host = self._rows_host.pin_memory()
+            self._rows_copied = None  # event: the last staging copy is done
+            self._rows_dev = []       # the table rows the device holds
+            self._row_samplers = []
+        return self._rows_io
+
+    def _row_sampler(self, b: int) -> DeviceSampler:
+        """Row b's sampler: its parameters and result live in row b of
+        row_params / rows_sample_out."""
+        while len(self._row_samplers) <= b:
+            i = len(self._row_samplers)
+            self._row_samplers.append(DeviceSampler(
+                self.cfg.vocab_size, self.device, params=self.row_params[i],
+                out=self.rows_sample_out[i], k=self.k))
+        return self._row_samplers[b]
+
+    def rows_logits(self, B: int | None = None) -> torch.Tensor:
+        """[B, vocab] logits the last row step left on device."""
+        out = self.logits_full if self.tp_path else self.logits0
+        return out[:B, : self.cfg.vocab_size]
+
+    def _stage_rows(self, tokens, slots, positions, params=None):
+        """Validate a ragged step and copy it to the device; returns
+        (B, table, decode_only). params: per-row (coin, temperature, topp)."""
+        from .rows import check_rows, is_decode_step
+        c, NB = self.cfg, self.n_batches
+        tokens, slots, positions = check_rows(
+            tokens, slots, positions, self.n_slots, c.seq_len, NB)
+        B = len(tokens)
+        self._rows_buffers()
+        if self._rows_copied is not None:
+            self._rows_copied.synchronize()  # the host twin is free again
+        host = self._rows_host
+        table = [(s * c.seq_len, p) for s, p in zip(slots, positions)]
+        host[:NB] = 0
+        host[:B] = torch.tensor(tokens, dtype=torch.int64)
+        hp = host[NB:5 * NB].view(torch.float64).view(NB, 4)
+        hp.zero_()  # temperature 0: a row nobody samples is an argmax
+        if params is not None:
+            hp[:B, :3] = torch.tensor(params, dtype=torch.float64)
+        words = 5 * NB
+        if self._rows_dev[:B] != table:
+            ht = host[5 * NB:].view(torch.int32).view(NB, 2)
+            ht.zero_()
+            ht[:B] = torch.tensor(table, dtype=torch.int32)
+            words = 6 * NB
+            self._rows_dev = list(table)
+        self._rows_io[:words].copy_(host[:words], non_blocking=True)
+        if self.device.type == "cuda":
+            self._rows_copied = torch.cuda.Event()
+            self._rows_copied.record(torch.cuda.current_stream(self.device))
+        return B, table, is_decode_step(slots)
+
+    def _forward_rows_buffers(self, B: int):
+        """One ragged step over row_tokens[:B] addressed by the row table:
+        forward_buffers' explicit-norm schedule with the unfused QKV matmul,
+        rope/KV write and attention per table row. All K/V rows are written
+        before the attention launch, so rows of one sequence (a prompt
+        chunk) see each other. Everything stays on device: capturable."""
+        c, k = self.cfg, self.k
+        NB = _pow2_batch(B)
+        self.ssq.zero_()
+        k.embed_gather(self.embedding, self.row_tokens, self.x, NB, self.ssq[0])
+        slot = 0
+        for l, lw in enumerate(self.layers):
+            self._norm_mm(lw["qkv"], lw["norm0"], slot, self.qkv_out, NB)
+            self._rope_kv_rows(l, lw, B)
+            self._attn_rows(l, B)
+            self._proj_merge(lw["wo"], self.zq, slot + 1, NB)
+            slot += 1
+            if c.is_moe:
+                self._norm_quant(lw["norm1"], slot, NB, self.t_norm[:NB])
+                self._moe_ffn(B, NB, lw, slot + 1)
+            else:
+                self._norm_mm(lw["w13"], lw["norm1"], slot, self.ff_out, NB)
+                self._swiglu_q80(self.ff_out, NB, self.dq,
+                                 c.hidden_act == HIDDEN_ACT_GELU)
+                self._proj_merge(lw["w2"], self.dq, slot + 1, NB)
+            slot += 1
+        self._logits(B, NB, slot, feedback=False)
+        if self.tp_path:
+            k.logits_concat(self.logits_full, self.logits_gather[NB], B)
+
+    def _rows_step_and_sample(self, B: int):
+        self._forward_rows_buffers(B)
+        logits = self.rows_logits(B)
+        for b in range(B):
+            self._row_sampler(b).launch(logits[b])
+
+    def _capture_rows_graph(self, B: int):
+        """Capture an all-decode step of B rows with its per-row samplers
+        and the table advance; None (and eager from then on) where capture
+        is unsupported."""
+        try:
+            for b in range(B):
+                self._row_sampler(b)  # buffers exist before the capture
+            torch.cuda.synchronize(self.device)
+            s = torch.cuda.Stream(self.device)
+            s.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.stream(s):
+                for _ in range(2):
+                    self._rows_step_and_sample(B)
+            torch.cuda.current_stream(self.device).wait_stream(s)
+            torch.cuda.synchronize(self.device)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._rows_step_and_sample(B)
+                self.k.rows_advance(self.rows, B)
+            self._row_graphs[B] = g
+            return g
+        except Exception as e:  # noqa: BLE001
+            import sys
+            if self.comm.rank == 0:
+                print(f"⚠️  row-step graph capture failed ({e}); "
+                      "running eager (slower)", file=sys.stderr)
+            self._row_graphs_failed = True
+            return None
+
+    def _run_rows(self, B: int, table, decode_only: bool, sample: bool):
+        """The staged step: a replay of the B-row graph when every row is a
+        decode row, else eager launches."""
+        sp = self._pick_splits(max(p for _, p in table))
+        if sp != self.attn_splits:
+            self._set_attn_splits(sp)  # drops the row graphs with the scratch
+        g = None
+        if (decode_only and self.row_graphs and not self._row_graphs_failed
+                and self.device.type == "cuda"):
+            g = self._row_graphs.get(B) or self._capture_rows_graph(B)
+        if g is not None:
+            g.replay()
+            # the graph's rows_advance moved every row on
+            self._rows_dev[:B] = [(base, p + 1) for base, p in table]
+        elif sample:
+            self._rows_step_and_sample(B)
+        else:
+            self._forward_rows_buffers(B)
+
+    def forward_rows(self, tokens, slots, positions) -> torch.Tensor:
+        """One ragged step: row b feeds tokens[b] at positions[b] of the
+        sequence in KV slot slots[b]; returns logits [B, vocab]. Rows may be
+        decode rows of different sequences, prompt chunks (several rows of
+        one slot at consecutive positions), or both. ValueError, before any
+        launch, for a slot >= n_slots, a position >= seq_len, a repeated
+        (slot, position) or more than n_batches rows."""
+        B, table, decode_only = self._stage_rows(tokens, slots, positions)
+        self._run_rows(B, table, decode_only, sample=False)
+        return self.rows_logits(B)
+
+    def forward_rows_sample(self, tokens, slots, positions, coins,
+                            temperatures, topps) -> list:
+        """forward_rows with every row's token sampled on device from its
+        own {coin, temperature, topp}: one token or None per row. None keeps
+        forward_sample's contract: resample that row on the host with the
+        same coin from rows_logits()."""
+        params = [(0.0 if c is None else float(c), float(t), float(p))
+                  for c, t, p in zip(coins, temperatures, topps)]
+        if len(params) != len(tokens):
+            raise ValueError("one coin, temperature and topp per row")
+        B, table, decode_only = self._stage_rows(tokens, slots, positions,
+                                                 params)
+        self._run_rows(B, table, decode_only, sample=True)
+        return [None if status else token
+                for token, status in self.rows_sample_out[:B].tolist()]
+
     # ------------------------------------------------------------ graphs
 
     def _pick_splits(self, pos: int) -> int:
@@ -902,6 +1136,7 @@ class HipTransformer:
             self.pos.fill_(pos_saved)
             self._graph_pos = pos_saved
         self._pf_graphs.clear()  # prefill graphs also reference the scratch
+        self._row_graphs.clear()  # and so do the row-step graphs
 
     def _warm_and_capture(self, B: int, warmups: int, advance_pos: bool = False,
                           sample: bool = False):

@@ -2,15 +2,37 @@
 
 #include "dllama_common.h"
 
+// ------------------------------------------------- row addressing policies
+// Which sequence position a batch row is, and where its sequence starts in
+// the KV cache. The positional kernels below are templated on one of these;
+// both read wave-uniform values (b is a blockIdx), so they stay scalar.
+//
+// SeqRows: row b is position pos[0]+b of the one cache (a prompt chunk or a
+// decode step of a single sequence).
+struct SeqRows {
+    const int *pos;
+    __device__ int position(int b) const { return pos[0] + b; }
+    __device__ int64_t cache_base(int) const { return 0; }
+};
+// TableRows: int32 [B, 2] = {cache_row_base, pos} per row, cache_row_base =
+// slot * seq_len: row b is position pos of the sequence whose cache rows
+// start at cache_row_base. Expresses N sequences decoding together, a prompt
+// chunk into any slot, and any mix of the two.
+struct TableRows {
+    const int *rows;
+    __device__ int position(int b) const { return rows[2 * b + 1]; }
+    __device__ int64_t cache_base(int b) const { return rows[2 * b]; }
+};
+
 // ------------------------------------------------- split-K flash decode
 // Stage 1: grid (H0, B, S); split sp covers t = (sp*4+wave) + 4*S*i — the
 // t-range is spread over S*4 waves so long contexts fill the chip.
 // Per-split (m, l, o) goes to scratch; stage 2 combines the S partials.
-template <int VEC, typename KVT, bool FUSE = false>
+template <int VEC, typename KVT, bool FUSE = false, typename ROWS = SeqRows>
 __global__ void k_attn_split(const float *__restrict__ q, int q_ld,
-                             const KVT *__restrict__ kc,
-                             const KVT *__restrict__ vc,
-                             const int *__restrict__ pos,
+                             const KVT *__restrict__ kc_all,
+                             const KVT *__restrict__ vc_all,
+                             const ROWS rows,
                              int n_heads0, int kv_mul, int kv_dim0, float scale,
                              float *__restrict__ ml_scratch,
                              float *__restrict__ o_scratch,
@@ -25,7 +47,10 @@ __global__ void k_attn_split(const float *__restrict__ q, int q_ld,
     const int sp = blockIdx.z;
     const int S = gridDim.z;
     const int hd = VEC * WAVE;
-    const int plen = pos[0] + b + 1;
+    // the row attends over cache rows base .. base+pos of its own sequence
+    const int plen = rows.position(b) + 1;
+    const KVT *kc = kc_all + rows.cache_base(b) * kv_dim0;
+    const KVT *vc = vc_all + rows.cache_base(b) * kv_dim0;
     const int wave = threadIdx.x / WAVE;
     const int lane = threadIdx.x % WAVE;
     const int kv_off = (h0 / kv_mul) * hd;
@@ -357,18 +382,19 @@ __global__ void k_rope(float *__restrict__ x,
 // the cache row pos+b, and copies v to the cache — one launch replacing
 // rope(q), rope(k), kv_append (reference runs 4 separate ops here,
 // llm.cpp:300-330).
-template <int STYLE, typename KVT>
+template <int STYLE, typename KVT, typename ROWS = SeqRows>
 __global__ void k_rope_kv(float *__restrict__ qkv, int ld,
                           int q_dim0, int kv_dim0,
                           const float *__restrict__ cache,
-                          const int *__restrict__ pos,
+                          const ROWS rows,
                           KVT *__restrict__ kc,
                           KVT *__restrict__ vc,
                           int hd) {
     const int b = blockIdx.y;
-    const int p = pos[0] + b;
+    const int rp = rows.position(b);          // rope position
+    const int64_t p = rows.cache_base(b) + rp;  // cache row written
     const int half = hd >> 1;
-    const float *pc = cache + (int64_t)p * hd;
+    const float *pc = cache + (int64_t)rp * hd;
     float *qrow = qkv + (int64_t)b * ld;
     float *krow = qrow + q_dim0;
     const float *vrow = krow + kv_dim0;
@@ -393,13 +419,13 @@ __global__ void k_rope_kv(float *__restrict__ qkv, int ld,
             const float o1 = v0 * ci + v1 * cr;
             if (is_q) { src[i0] = o0; src[i1] = o1; }
             else {
-                KVT *dst = kc + (int64_t)p * kv_dim0;
+                KVT *dst = kc + p * kv_dim0;
                 dst[i0] = kv_c<KVT>(o0); dst[i1] = kv_c<KVT>(o1);
             }
         } else {
             const int j = (i - qp - kp) * 4;
             const float4 vv = *reinterpret_cast<const float4 *>(vrow + j);
-            KVT *dst = vc + (int64_t)p * kv_dim0 + j;
+            KVT *dst = vc + p * kv_dim0 + j;
             dst[0] = kv_c<KVT>(vv.x); dst[1] = kv_c<KVT>(vv.y);
             dst[2] = kv_c<KVT>(vv.z); dst[3] = kv_c<KVT>(vv.w);
         }
@@ -430,27 +456,28 @@ __global__ void k_kv_append(const float *__restrict__ k,
 // cache write (reference rope + shift ops). One workgroup (1 wave) per head:
 // q heads normalize+rotate in place, k heads normalize+rotate into the
 // cache, v heads copy to the cache.
-template <typename KVT>
+template <typename KVT, typename ROWS = SeqRows>
 __global__ void k_rope_kv_qknorm(float *__restrict__ qkv, int ld,
                                  int q_dim0, int kv_dim0,
                                  const float *__restrict__ cache,
-                                 const int *__restrict__ pos,
+                                 const ROWS rows,
                                  KVT *__restrict__ kc, KVT *__restrict__ vc,
                                  int hd,
                                  const float *__restrict__ wq,
                                  const float *__restrict__ wk, float eps) {
     const int b = blockIdx.y;
-    const int p = pos[0] + b;
+    const int rp = rows.position(b);          // rope position
+    const int64_t p = rows.cache_base(b) + rp;  // cache row written
     const int h = blockIdx.x;
     const int qh = q_dim0 / hd, kvh = kv_dim0 / hd;
     const int half = hd >> 1;
-    const float *pc = cache + (int64_t)p * hd;
+    const float *pc = cache + (int64_t)rp * hd;
     const int lane = threadIdx.x;  // blockDim == 64
     if (h >= qh + kvh) {
         // v head: plain copy into the cache
         const int hv = h - qh - kvh;
         const float *src = qkv + (int64_t)b * ld + q_dim0 + kv_dim0 + hv * hd;
-        KVT *dst = vc + (int64_t)p * kv_dim0 + hv * hd;
+        KVT *dst = vc + p * kv_dim0 + hv * hd;
         for (int i = lane; i < hd; i += WAVE) dst[i] = kv_c<KVT>(src[i]);
         return;
     }
@@ -475,11 +502,17 @@ __global__ void k_rope_kv_qknorm(float *__restrict__ qkv, int ld,
             row[j] = o0;
             row[j + half] = o1;
         } else {
-            KVT *dst = kc + (int64_t)p * kv_dim0 + (h - qh) * hd;
+            KVT *dst = kc + p * kv_dim0 + (h - qh) * hd;
             dst[j] = kv_c<KVT>(o0);
             dst[j + half] = kv_c<KVT>(o1);
         }
     }
+}
+
+// Row table [B, 2]: every row's pos += 1 (its cache_row_base stays).
+__global__ void k_rows_advance(int *__restrict__ rows, int batch) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < batch) rows[2 * b + 1] += 1;
 }
 
 // ============================================================== host bindings
@@ -534,13 +567,31 @@ void kv_append(torch::Tensor k, torch::Tensor v, torch::Tensor kc,
     });
 }
 
-void attn(torch::Tensor q, int64_t q_ld, torch::Tensor kc, torch::Tensor vc,
-          torch::Tensor y, torch::Tensor pos, int64_t batch, int64_t n_heads0,
-          int64_t kv_mul, int64_t head_dim, int64_t splits,
-          torch::Tensor ml_scratch, torch::Tensor o_scratch, torch::Tensor counter,
-          c10::optional<torch::Tensor> zq = c10::nullopt,
-          c10::optional<torch::Tensor> zs = c10::nullopt,
-          c10::optional<torch::Tensor> zbs = c10::nullopt) {
+// A row table as the kernels read it: int32 [>= batch, 2], contiguous, on
+// the device. Its contents (slot bases and positions inside the caches) are
+// the caller's to validate: the host never sees them in a captured step.
+static TableRows table_rows(const torch::Tensor &rows, int64_t batch) {
+    CHECK_CUDA(rows);
+    TORCH_CHECK(rows.scalar_type() == at::kInt && rows.dim() == 2
+                && rows.size(1) == 2 && rows.is_contiguous()
+                && rows.size(0) >= batch,
+                "row table must be a contiguous int32 [>= batch, 2]");
+    return TableRows{rows.data_ptr<int>()};
+}
+
+// Split + combine launches of attention, for either row addressing. The
+// GQA-grouped experiment and the S==1 fused kernel (allow_variants) exist
+// for the single-sequence form only.
+template <typename ROWS>
+static void attn_launch(torch::Tensor &q, int64_t q_ld, torch::Tensor &kc,
+                        torch::Tensor &vc, torch::Tensor &y, ROWS rows,
+                        int64_t batch, int64_t n_heads0, int64_t kv_mul,
+                        int64_t head_dim, int64_t splits,
+                        torch::Tensor &ml_scratch, torch::Tensor &o_scratch,
+                        int *counter, bool allow_variants,
+                        c10::optional<torch::Tensor> &zq,
+                        c10::optional<torch::Tensor> &zs,
+                        c10::optional<torch::Tensor> &zbs) {
     CHECK_CUDA(q);
     const int kv_dim0 = kc.size(1);
     const float scale = 1.0f / sqrtf((float)head_dim);
@@ -559,40 +610,46 @@ void attn(torch::Tensor q, int64_t q_ld, torch::Tensor kc, torch::Tensor vc,
     // more than the saved traffic. Kept behind DLLAMA_GQA_ATTN=1.
     static const bool env_gqa =
         std::getenv("DLLAMA_GQA_ATTN") && atoi(std::getenv("DLLAMA_GQA_ATTN")) == 1;
-    const bool gqa = env_gqa && kv_mul > 1 && kv_mul <= 8
+    const bool gqa = allow_variants && env_gqa && kv_mul > 1 && kv_mul <= 8
         && n_heads0 % kv_mul == 0 && splits > 1;
     // splits==1 + quant output: single fused kernel (normalize + Q80 emit
     // in the split kernel), no combine launch
-    const bool fused = !gqa && splits == 1 && quant;
+    const bool fused = allow_variants && !gqa && splits == 1 && quant;
     with_head_vec(head_dim, [&](auto vec_const) {
         constexpr int V = decltype(vec_const)::value;
         with_kv_ptrs(kc, vc, [&](auto *kcp, auto *vcp) {
             using KVT = std::remove_pointer_t<decltype(kcp)>;
             auto split = [&](auto fuse_const) {
                 constexpr bool FUSE = decltype(fuse_const)::value;
-                hipLaunchKernelGGL((k_attn_split<V, KVT, FUSE>), grid, dim3(256), 0,
+                hipLaunchKernelGGL((k_attn_split<V, KVT, FUSE, ROWS>), grid,
+                                   dim3(256), 0,
                                    cur_stream(), q.data_ptr<float>(), (int)q_ld,
-                                   kcp, vcp, pos.data_ptr<int>(),
+                                   kcp, vcp, rows,
                                    (int)n_heads0, (int)kv_mul, kv_dim0, scale,
                                    ml_scratch.data_ptr<float>(),
                                    o_scratch.data_ptr<float>(),
-                                   counter.data_ptr<int>(), nullptr,
+                                   counter, nullptr,
                                    FUSE ? zqp : nullptr, FUSE ? zsp : nullptr,
                                    FUSE ? zbsp : nullptr);
             };
-            if (gqa)
-                hipLaunchKernelGGL((k_attn_split_gqa<V, KVT>),
-                                   dim3(n_heads0 / kv_mul, batch, splits),
-                                   dim3(kv_mul * WAVE), 0,
-                                   cur_stream(), q.data_ptr<float>(), (int)q_ld,
-                                   kcp, vcp, pos.data_ptr<int>(), (int)n_heads0,
-                                   (int)kv_mul, kv_dim0, scale,
-                                   ml_scratch.data_ptr<float>(),
-                                   o_scratch.data_ptr<float>());
-            else if (fused)
-                split(std::true_type{});
-            else
-                split(std::false_type{});
+            if constexpr (std::is_same_v<ROWS, SeqRows>) {
+                if (gqa) {
+                    hipLaunchKernelGGL((k_attn_split_gqa<V, KVT>),
+                                       dim3(n_heads0 / kv_mul, batch, splits),
+                                       dim3(kv_mul * WAVE), 0,
+                                       cur_stream(), q.data_ptr<float>(), (int)q_ld,
+                                       kcp, vcp, rows.pos, (int)n_heads0,
+                                       (int)kv_mul, kv_dim0, scale,
+                                       ml_scratch.data_ptr<float>(),
+                                       o_scratch.data_ptr<float>());
+                    return;
+                }
+                if (fused) {
+                    split(std::true_type{});
+                    return;
+                }
+            }
+            split(std::false_type{});
         });
         if (fused) return;
         auto combine = [&](auto quant_const) {
@@ -607,19 +664,83 @@ void attn(torch::Tensor q, int64_t q_ld, torch::Tensor kc, torch::Tensor vc,
     });
 }
 
-void rope_kv(torch::Tensor qkv, int64_t ld, int64_t q_dim0, int64_t kv_dim0,
-             torch::Tensor cache, torch::Tensor pos, torch::Tensor kc,
-             torch::Tensor vc, int64_t head_dim, int64_t style, int64_t batch) {
+void attn(torch::Tensor q, int64_t q_ld, torch::Tensor kc, torch::Tensor vc,
+          torch::Tensor y, torch::Tensor pos, int64_t batch, int64_t n_heads0,
+          int64_t kv_mul, int64_t head_dim, int64_t splits,
+          torch::Tensor ml_scratch, torch::Tensor o_scratch, torch::Tensor counter,
+          c10::optional<torch::Tensor> zq = c10::nullopt,
+          c10::optional<torch::Tensor> zs = c10::nullopt,
+          c10::optional<torch::Tensor> zbs = c10::nullopt) {
+    attn_launch(q, q_ld, kc, vc, y, SeqRows{pos.data_ptr<int>()}, batch,
+                n_heads0, kv_mul, head_dim, splits, ml_scratch, o_scratch,
+                counter.data_ptr<int>(), true, zq, zs, zbs);
+}
+
+// Row b attends over cache rows base_b .. base_b+pos_b of the row table;
+// always the split + combine pair.
+void attn_rows(torch::Tensor q, int64_t q_ld, torch::Tensor kc, torch::Tensor vc,
+               torch::Tensor y, torch::Tensor rows, int64_t batch,
+               int64_t n_heads0, int64_t kv_mul, int64_t head_dim,
+               int64_t splits, torch::Tensor ml_scratch, torch::Tensor o_scratch,
+               c10::optional<torch::Tensor> zq = c10::nullopt,
+               c10::optional<torch::Tensor> zs = c10::nullopt,
+               c10::optional<torch::Tensor> zbs = c10::nullopt) {
+    attn_launch(q, q_ld, kc, vc, y, table_rows(rows, batch), batch, n_heads0,
+                kv_mul, head_dim, splits, ml_scratch, o_scratch, nullptr,
+                false, zq, zs, zbs);
+}
+
+template <typename ROWS>
+static void rope_kv_launch(torch::Tensor &qkv, int64_t ld, int64_t q_dim0,
+                           int64_t kv_dim0, torch::Tensor &cache, ROWS rows,
+                           torch::Tensor &kc, torch::Tensor &vc,
+                           int64_t head_dim, int64_t style, int64_t batch) {
     CHECK_CUDA(qkv);
     const int total = (int)(q_dim0 / 2 + kv_dim0 / 2 + kv_dim0 / 4);
     const dim3 grid(ceil_div(total, 256), batch);
     with_kv_ptrs(kc, vc, [&](auto *kcp, auto *vcp) {
         using KVT = std::remove_pointer_t<decltype(kcp)>;
-        auto *kern = style == 0 ? k_rope_kv<0, KVT> : k_rope_kv<1, KVT>;
+        auto *kern = style == 0 ? k_rope_kv<0, KVT, ROWS> : k_rope_kv<1, KVT, ROWS>;
         hipLaunchKernelGGL(kern, grid, dim3(256), 0, cur_stream(),
                            qkv.data_ptr<float>(), (int)ld, (int)q_dim0, (int)kv_dim0,
-                           cache.data_ptr<float>(), pos.data_ptr<int>(),
+                           cache.data_ptr<float>(), rows,
                            kcp, vcp, (int)head_dim);
+    });
+}
+
+void rope_kv(torch::Tensor qkv, int64_t ld, int64_t q_dim0, int64_t kv_dim0,
+             torch::Tensor cache, torch::Tensor pos, torch::Tensor kc,
+             torch::Tensor vc, int64_t head_dim, int64_t style, int64_t batch) {
+    rope_kv_launch(qkv, ld, q_dim0, kv_dim0, cache,
+                   SeqRows{pos.data_ptr<int>()}, kc, vc, head_dim, style, batch);
+}
+
+void rope_kv_rows(torch::Tensor qkv, int64_t ld, int64_t q_dim0, int64_t kv_dim0,
+                  torch::Tensor cache, torch::Tensor rows, torch::Tensor kc,
+                  torch::Tensor vc, int64_t head_dim, int64_t style,
+                  int64_t batch) {
+    rope_kv_launch(qkv, ld, q_dim0, kv_dim0, cache, table_rows(rows, batch),
+                   kc, vc, head_dim, style, batch);
+}
+
+template <typename ROWS>
+static void rope_kv_qknorm_launch(torch::Tensor &qkv, int64_t ld, int64_t q_dim0,
+                                  int64_t kv_dim0, torch::Tensor &cache,
+                                  ROWS rows, torch::Tensor &kc,
+                                  torch::Tensor &vc, int64_t head_dim,
+                                  torch::Tensor &wq, torch::Tensor &wk,
+                                  double eps, int64_t batch) {
+    CHECK_CUDA(qkv);
+    const int heads = (int)((q_dim0 + 2 * kv_dim0) / head_dim);
+    const dim3 grid(heads, batch);
+    with_kv_ptrs(kc, vc, [&](auto *kcp, auto *vcp) {
+        using KVT = std::remove_pointer_t<decltype(kcp)>;
+        hipLaunchKernelGGL((k_rope_kv_qknorm<KVT, ROWS>), grid, dim3(WAVE), 0,
+                           cur_stream(), qkv.data_ptr<float>(), (int)ld,
+                           (int)q_dim0, (int)kv_dim0, cache.data_ptr<float>(),
+                           rows, kcp, vcp, (int)head_dim,
+                           wq.data_ptr<float>(), wk.data_ptr<float>(),
+                           (float)eps);
     });
 }
 
@@ -628,24 +749,43 @@ void rope_kv_qknorm(torch::Tensor qkv, int64_t ld, int64_t q_dim0,
                     torch::Tensor kc, torch::Tensor vc, int64_t head_dim,
                     torch::Tensor wq, torch::Tensor wk, double eps,
                     int64_t batch) {
-    CHECK_CUDA(qkv);
-    const int heads = (int)((q_dim0 + 2 * kv_dim0) / head_dim);
-    const dim3 grid(heads, batch);
-    with_kv_ptrs(kc, vc, [&](auto *kcp, auto *vcp) {
-        using KVT = std::remove_pointer_t<decltype(kcp)>;
-        hipLaunchKernelGGL((k_rope_kv_qknorm<KVT>), grid, dim3(WAVE), 0,
-                           cur_stream(), qkv.data_ptr<float>(), (int)ld,
-                           (int)q_dim0, (int)kv_dim0, cache.data_ptr<float>(),
-                           pos.data_ptr<int>(), kcp, vcp, (int)head_dim,
-                           wq.data_ptr<float>(), wk.data_ptr<float>(),
-                           (float)eps);
-    });
+    rope_kv_qknorm_launch(qkv, ld, q_dim0, kv_dim0, cache,
+                          SeqRows{pos.data_ptr<int>()}, kc, vc, head_dim, wq,
+                          wk, eps, batch);
+}
+
+void rope_kv_qknorm_rows(torch::Tensor qkv, int64_t ld, int64_t q_dim0,
+                         int64_t kv_dim0, torch::Tensor cache,
+                         torch::Tensor rows, torch::Tensor kc, torch::Tensor vc,
+                         int64_t head_dim, torch::Tensor wq, torch::Tensor wk,
+                         double eps, int64_t batch) {
+    rope_kv_qknorm_launch(qkv, ld, q_dim0, kv_dim0, cache,
+                          table_rows(rows, batch), kc, vc, head_dim, wq, wk,
+                          eps, batch);
+}
+
+// pos += 1 in the first `batch` rows of a row table: a captured all-decode
+// step advances itself, as pos_inc does for the single sequence
+void rows_advance(torch::Tensor rows, int64_t batch) {
+    table_rows(rows, batch);
+    hipLaunchKernelGGL(k_rows_advance, dim3(ceil_div((int)batch, WAVE)),
+                       dim3(WAVE), 0, cur_stream(), rows.data_ptr<int>(),
+                       (int)batch);
 }
 
 void register_attn(py::module &m) {
     m.def("rope_kv_qknorm", &rope_kv_qknorm);
+    m.def("rope_kv_qknorm_rows", &rope_kv_qknorm_rows);
     m.def("rope", &rope);
     m.def("rope_kv", &rope_kv);
+    m.def("rope_kv_rows", &rope_kv_rows);
+    m.def("rows_advance", &rows_advance);
+    m.def("attn_rows", &attn_rows, py::arg("q"), py::arg("q_ld"), py::arg("kc"),
+          py::arg("vc"), py::arg("y"), py::arg("rows"), py::arg("batch"),
+          py::arg("n_heads0"), py::arg("kv_mul"), py::arg("head_dim"),
+          py::arg("splits"), py::arg("ml_scratch"), py::arg("o_scratch"),
+          py::arg("zq") = py::none(), py::arg("zs") = py::none(),
+          py::arg("zbs") = py::none());
     m.def("kv_append", &kv_append);
     m.def("attn", &attn, py::arg("q"), py::arg("q_ld"), py::arg("kc"), py::arg("vc"),
           py::arg("y"), py::arg("pos"), py::arg("batch"), py::arg("n_heads0"),

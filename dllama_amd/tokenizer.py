@@ -182,6 +182,14 @@ class Tokenizer:
     def reset_decoder(self) -> None:
         self._decode_buf.clear()
 
+    def fork_decoder(self) -> "Tokenizer":
+        """This tokenizer with a streaming-decode state of its own (the
+        vocabulary is shared): one per sequence decoded concurrently."""
+        import copy
+        t = copy.copy(self)
+        t._decode_buf = bytearray()
+        return t
+
     def decode(self, token: int) -> str | None:
         """Streaming decode of one token; returns printable text or None
         while mid-UTF-8-sequence (reference src/tokenizer.cpp:291-309)."""
