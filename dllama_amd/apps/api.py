@@ -12,7 +12,9 @@ Behavior parity with the reference API server (src/dllama-api.cpp):
   - --slots N > 1 (one GPU): a threading server whose handlers enqueue
     requests to one scheduler thread; it owns the model and a BatchEngine
     and decodes up to N requests per step. Each request prefills from 0
-    there (no NaiveCache reuse across slots).
+    there (no NaiveCache reuse across slots) unless --kv-pages M pages the
+    KV cache: then whole pages of a shared prompt prefix or chat history
+    are reused across slots (usage.prompt_tokens_details.cached_tokens).
 """
 
 from __future__ import annotations
@@ -68,19 +70,25 @@ class BatchScheduler:
         self.thread = threading.Thread(target=self._loop, daemon=True)
         self.thread.start()
 
-    def submit(self, tokens, max_tokens, sampler, on_token, stop_check, on_done):
-        """on_done(error_or_None) is called once, after the last on_token."""
+    def submit(self, tokens, max_tokens, sampler, on_token, stop_check, on_done,
+               stats_out=None):
+        """on_done(error_or_None) is called once, after the last on_token.
+        stats_out: a list that receives the sequence's GenStats when it is
+        queued in the engine."""
         self.inbox.put((tokens, max_tokens, sampler, on_token, stop_check,
-                        on_done))
+                        on_done, stats_out))
 
     def stop(self):
         self.inbox.put(None)
         self.thread.join()
 
     def _admit(self, item):
-        *request, on_done = item
+        *request, on_done, stats_out = item
         try:
-            self.active.append((self.engine.submit(*request), on_done))
+            seq = self.engine.submit(*request)
+            if stats_out is not None:
+                stats_out.append(seq.stats)
+            self.active.append((seq, on_done))
         except Exception as e:  # noqa: BLE001  (e.g. prompt beyond seq_len)
             on_done(e)
 
@@ -216,10 +224,12 @@ class ApiState:
                     deltas.put(delta)
                     detector.reset()
 
+        stats = []
         self.scheduler.submit(
             tokens, int(body.get("max_tokens") or 256), sampler, on_token,
             lambda t: detector.is_eos(t) or detector.eos_pos >= 0,
-            lambda error: deltas.put(error if error is not None else StopIteration))
+            lambda error: deltas.put(error if error is not None else StopIteration),
+            stats)
         out_text = []
         while True:
             item = deltas.get()
@@ -229,7 +239,10 @@ class ApiState:
                 raise item
             out_text.append(item)
             emit(item)
-        return "".join(out_text), len(tokens), generated[0]
+        # a fourth value on this path only: the prompt tokens that came from
+        # shared KV pages (0 on an unpaged model)
+        return ("".join(out_text), len(tokens), generated[0],
+                stats[0].cached_tokens if stats else 0)
 
 
 STATE: ApiState | None = None
@@ -298,19 +311,22 @@ class Handler(BaseHTTPRequestHandler):
                 self.wfile.write(b"0\r\n\r\n")
         else:
             try:
-                text, n_prompt, n_gen = STATE.complete(body, lambda d: None)
+                text, n_prompt, n_gen, *cached = STATE.complete(
+                    body, lambda d: None)
             except Exception as e:  # noqa: BLE001
                 self._json(500, {"error": {"message": str(e), "type": "server_error"}})
                 return
+            usage = {"prompt_tokens": n_prompt, "completion_tokens": n_gen,
+                     "total_tokens": n_prompt + n_gen}
+            if cached:  # the batched path
+                usage["prompt_tokens_details"] = {"cached_tokens": cached[0]}
             self._json(200, {
                 "id": rid, "object": "chat.completion", "created": created,
                 "model": STATE.model_name,
                 "choices": [{"index": 0, "message":
                              {"role": "assistant", "content": text},
                              "finish_reason": "stop"}],
-                "usage": {"prompt_tokens": n_prompt,
-                          "completion_tokens": n_gen,
-                          "total_tokens": n_prompt + n_gen}})
+                "usage": usage})
 
     def _chunk(self, s: str):
         data = s.encode()

@@ -44,6 +44,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--slots", type=int, default=1,
                    help="KV slots = sequences decoded per step (--prompt-file, "
                         "dllama-api); 1 is the single-sequence path")
+    p.add_argument("--kv-pages", type=int, default=0,
+                   help="with --slots > 1: keep the KV cache as a pool of this "
+                        "many pages shared by all slots, with prompt prefixes "
+                        "reused across sequences; 0 (default) reserves "
+                        "--max-seq-len rows per slot")
+    p.add_argument("--page-size", type=int, default=64,
+                   help="rows per KV page (--kv-pages): a power of two, 4..256")
     p.add_argument("--steps", type=int, default=64)
     p.add_argument("--buffer-float-type", default="q80", choices=["q80", "f32"],
                    help="TP sync buffer quantization (reference --buffer-float-type)")
@@ -93,19 +100,39 @@ def load_engine(args):
             f"error: --slots {slots} needs a single GPU (world is "
             f"{comm.world}): multi-slot serving under tensor parallelism is "
             "not supported yet")
+    kv_pages = getattr(args, "kv_pages", 0)
+    page_size = getattr(args, "page_size", 64)
+    if kv_pages < 0:
+        raise SystemExit("error: --kv-pages must be >= 0")
+    if kv_pages and comm.world > 1:
+        raise SystemExit(
+            f"error: --kv-pages {kv_pages} needs a single GPU (world is "
+            f"{comm.world}): multi-slot serving under tensor parallelism is "
+            "not supported yet")
+    if kv_pages and slots < 2:
+        raise SystemExit(
+            "error: --kv-pages needs --slots > 1: a paged KV cache serves "
+            "the multi-slot path (--prompt-file, dllama-api)")
+    if kv_pages:
+        from ..models.rows import PAGE_SIZES
+        if page_size not in PAGE_SIZES:
+            raise SystemExit(
+                f"error: --page-size must be a power of two in 4..256 "
+                f"(got {page_size})")
+    paging = dict(kv_pages=kv_pages, page_size=page_size) if kv_pages else {}
     sync = Q80 if args.buffer_float_type == "q80" else F32
     m = mf.ModelFile(args.model, max_seq_len=args.max_seq_len, sync_type=sync)
     use_gpu = torch.cuda.is_available() and args.gpu_index != -1
     cfg = ModelConfig.from_header(m.header, world=comm.world, rank=comm.rank)
     if comm.rank == 0:
-        _print_header(m.header, cfg, use_gpu, slots)
+        _print_header(m.header, cfg, use_gpu, slots, kv_pages, page_size)
     if use_gpu:
         from ..models.hip_model import HipTransformer
         dev = args.gpu_index if args.gpu_index is not None \
             else int(os.environ.get("LOCAL_RANK", "0"))
         model = HipTransformer.from_file(m, cfg, device=f"cuda:{dev}", comm=comm,
                                          n_batches=args.n_batches,
-                                         n_slots=slots)
+                                         n_slots=slots, **paging)
         # fused temperature/top-p sampler in the captured decode step; read
         # before the capture, which is what puts it into the graph.
         # DLLAMA_DEVICE_SAMPLER=0 keeps sampling in Sampler.sample_torch
@@ -130,7 +157,7 @@ def load_engine(args):
         wdt = ("q40" if args.cpu_dtype == "q40"
                else torch.float16 if args.cpu_dtype == "f16" else torch.float32)
         model = CpuTransformer(m, cfg, comm, weight_dtype=wdt, n_slots=slots,
-                               n_batches=args.n_batches)
+                               n_batches=args.n_batches, **paging)
     tok = Tokenizer(args.tokenizer) if args.tokenizer else None
     seed = args.seed if args.seed is not None else int(time.time())
     if comm.world > 1:
@@ -145,7 +172,7 @@ def load_engine(args):
     return InferenceEngine(model, tok, sampler, n_batches=nb), m, comm
 
 
-def _print_header(h, cfg, use_gpu, slots=1):
+def _print_header(h, cfg, use_gpu, slots=1, kv_pages=0, page_size=64):
     print(f"💡 Arch: {'Llama' if h.arch_type == mf.ARCH_LLAMA else 'Qwen3 MoE' if h.arch_type == mf.ARCH_QWEN3_MOE else 'Qwen3'}")
     print(f"💡 Dim: {h.dim}\n💡 HiddenDim: {h.hidden_dim}\n💡 nLayers: {h.n_layers}")
     print(f"💡 nHeads: {h.n_heads}\n💡 nKvHeads: {h.n_kv_heads}\n💡 HeadDim: {h.head_dim}")
@@ -155,11 +182,17 @@ def _print_header(h, cfg, use_gpu, slots=1):
     print(f"💡 Backend: {'MI355X HIP' if use_gpu else 'CPU'}  TP={cfg.world}")
     # memory accounting (reference 📀 prints, nn-core.cpp:175-189): per-rank
     # resident weight shard + dense f32 KV cache
-    kv_bytes = 2 * cfg.n_layers * cfg.seq_len * cfg.kv_dim0 * 4 * slots
+    kv_rows = kv_pages * page_size if kv_pages else cfg.seq_len * slots
+    kv_bytes = 2 * cfg.n_layers * kv_rows * cfg.kv_dim0 * 4
     weights = h.file_size - h.header_size  # .m = header + packed weights
+    if kv_pages:
+        shape = (f"{kv_pages} pages x {page_size} rows shared by "
+                 f"{slots} slots, seq {cfg.seq_len})")
+    else:
+        shape = (f"seq {cfg.seq_len}"
+                 + (f" x {slots} slots)" if slots > 1 else ")"))
     print(f"📀 Weights/rank: {weights / max(1, cfg.world) / 1e9:.2f} GB"
-          f"  KV cache/rank: {kv_bytes / 1e9:.2f} GB (seq {cfg.seq_len}"
-          + (f" x {slots} slots)" if slots > 1 else ")"))
+          f"  KV cache/rank: {kv_bytes / 1e9:.2f} GB ({shape}")
 
 
 def run_inference(args) -> int:
@@ -244,8 +277,10 @@ def run_inference_many(args, engine) -> int:
     n_pred = sum(st.decode_tokens for _, st in results)
     eval_s = n_eval / max(sum(st.prefill_time for _, st in results), 1e-9)
     pred_s = n_pred / max(wall, 1e-9)
+    n_cached = sum(st.cached_tokens for _, st in results)
     print(f"Evaluation\n   nBatches: {args.n_batches}\n   nTokens: {n_eval}\n"
-          f"   tokens/s: {eval_s:.2f} ({1000.0 / max(eval_s, 1e-9):.2f} ms/tok)")
+          + (f"   nCachedTokens: {n_cached}\n" if batch.pool is not None else "")
+          + f"   tokens/s: {eval_s:.2f} ({1000.0 / max(eval_s, 1e-9):.2f} ms/tok)")
     print(f"Prediction\n   nSequences: {len(prompts)} in {args.slots} slots\n"
           f"   nTokens: {n_pred}\n"
           f"   tokens/s: {pred_s:.2f} aggregate "

@@ -31,6 +31,9 @@ class GenStats:
     prefill_time: float = 0.0
     decode_tokens: int = 0
     decode_time: float = 0.0
+    # prompt tokens whose K/V came from shared prefix pages (BatchEngine on
+    # a paged model); they were not stepped
+    cached_tokens: int = 0
 
     @property
     def eval_tok_s(self) -> float:
@@ -175,7 +178,10 @@ class _Sequence:
         self.on_token = on_token
         self.stop_check = stop_check
         self.slot = None      # KV slot while running
-        self.fed = 0          # prompt tokens already stepped
+        self.fed = 0          # prompt tokens already stepped (or shared)
+        self.pages = []       # paged model: pool pages held, by page index
+        self.registered = 0   # ... of which the first so many are indexed
+        self.written = 0      # positions whose K/V the slot holds
         self.out: list[int] = []
         self.done = False
         self.stats = GenStats(prefill_tokens=len(self.prompt))
@@ -200,12 +206,29 @@ class BatchEngine:
     still prefilling, in submission order. Sequences beyond the slot count
     wait; a finished sequence frees its slot for the next. Each sequence
     owns its Sampler (its own RNG stream), so what it generates does not
-    depend on what it is batched with."""
+    depend on what it is batched with.
 
-    def __init__(self, model, tokenizer=None, n_batches: int = 32):
+    On a paged model (kv_pages > 0) a sequence also needs pages: admission
+    is FIFO and takes a free slot plus every page the sequence can come to
+    use, reserved up front, so nothing runs out mid-flight and nothing is
+    preempted. If the head of the queue does not fit it waits, and nothing
+    overtakes it. With share_prefixes the leading full pages of a prompt
+    that are cached in the pool's prefix index are mapped instead of
+    computed (stats.cached_tokens), and every page a sequence fills, prompt
+    or generated, is registered for later requests."""
+
+    def __init__(self, model, tokenizer=None, n_batches: int = 32,
+                 share_prefixes: bool = True):
         if not hasattr(model, "forward_rows"):
             raise ValueError("BatchEngine needs a model with forward_rows")
         self.model = model
+        self.pool = None
+        if getattr(model, "page_map", None) is not None:
+            from .models.pages import PagePool
+            self.pool = PagePool(model.kv_pages, model.page_size,
+                                 share=share_prefixes)
+            for slot in range(model.n_slots):
+                model.clear_slot(slot)
         self.tokenizer = tokenizer
         self.n_batches = min(n_batches, getattr(model, "n_batches", n_batches))
         self.seq_len = model.cfg.seq_len
@@ -234,6 +257,13 @@ class BatchEngine:
             raise ValueError(
                 f"prompt of {len(prompt_tokens)} tokens exceeds seq_len "
                 f"{self.seq_len} (rebuild with a larger --max-seq-len / seq_len)")
+        if self.pool is not None:
+            need = self._pages_needed(len(prompt_tokens), max_tokens)
+            if need > self.pool.n_pages:
+                raise ValueError(
+                    f"a request of {len(prompt_tokens)} prompt tokens and "
+                    f"max_tokens {max_tokens} needs {need} KV pages, the pool "
+                    f"has {self.pool.n_pages} (raise --kv-pages / kv_pages)")
         if sampler is None:
             sampler = Sampler(self.model.cfg.vocab_size, 0.0, 0.9, 12345)
         seq = _Sequence(prompt_tokens, max_tokens, sampler, on_token,
@@ -245,11 +275,47 @@ class BatchEngine:
     def idle(self) -> bool:
         return not self.waiting and not self.running
 
+    def _pages_needed(self, n_prompt: int, max_tokens: int) -> int:
+        P = self.pool.page_size
+        return -(-min(n_prompt + max_tokens, self.seq_len) // P)
+
+    def _take_pages(self, seq: _Sequence) -> bool:
+        """Reserve the pages of the sequence's whole life: the cached
+        pages of its prompt's prefix, shared, plus new ones. False, with
+        nothing taken, when the pool cannot supply them now."""
+        pool = self.pool
+        shared = pool.match(seq.prompt)
+        need = self._pages_needed(len(seq.prompt), seq.max_tokens)
+        new = pool.alloc(need - len(shared))
+        if new is None:
+            pool.release(shared)
+            return False
+        seq.pages = shared + new
+        seq.registered = len(shared)
+        seq.fed = seq.written = len(shared) * pool.page_size
+        seq.stats.cached_tokens = seq.fed
+        return True
+
+    def _register_pages(self, seq: _Sequence) -> None:
+        """Index the pages the sequence has filled since the last step."""
+        P = self.pool.page_size
+        while (seq.registered + 1) * P <= seq.written:
+            n = (seq.registered + 1) * P
+            fed = seq.prompt[:n]
+            fed += seq.out[: n - len(fed)]
+            self.pool.register(fed, seq.pages[seq.registered])
+            seq.registered += 1
+
     def _plan(self):
         """Rows of the next step as (sequence, token, position, samples)."""
         while self.waiting and self.free_slots:
-            seq = self.waiting.pop(0)
+            seq = self.waiting[0]
+            if self.pool is not None and not self._take_pages(seq):
+                break  # the head waits for pages; nothing overtakes it
+            self.waiting.pop(0)
             seq.slot = self.free_slots.pop(0)
+            if self.pool is not None:
+                self.model.set_slot_pages(seq.slot, seq.pages)
             self.running.append(seq)
         rows = []
         for seq in self.running:
@@ -302,9 +368,14 @@ class BatchEngine:
             picked = [seq.sampler.sample(logits[b]) if smp else None
                       for b, (seq, _, _, smp) in enumerate(rows)]
         now = time.perf_counter()
-        for b, (seq, _, pos, smp) in enumerate(rows):
+        for seq, _, pos, _ in rows:
             if seq.prefilling:
                 seq.fed += 1
+            seq.written = pos + 1  # a sequence's rows are in position order
+        if self.pool is not None:
+            for seq in self.running:
+                self._register_pages(seq)
+        for b, (seq, _, pos, smp) in enumerate(rows):
             if smp:
                 self._accept(seq, int(picked[b]), now)
 
@@ -324,6 +395,10 @@ class BatchEngine:
             seq.stats.decode_tokens = len(seq.out)
             seq.stats.decode_time = now - seq._t0
             self.running.remove(seq)
+            if self.pool is not None:
+                self.pool.release(seq.pages)
+                self.model.clear_slot(seq.slot)
+                seq.pages = []
             self.free_slots.append(seq.slot)
             self.free_slots.sort()
             seq.slot = None

@@ -42,10 +42,21 @@ class Q40W:
 class CpuTransformer:
     def __init__(self, m: ModelFile, config: ModelConfig, comm: Comm | None = None,
                  activation_quant: bool = True, weight_dtype: torch.dtype = torch.float32,
-                 n_slots: int = 1, n_batches: int = 32):
+                 n_slots: int = 1, n_batches: int = 32, kv_pages: int = 0,
+                 page_size: int = 64):
         self.cfg = config
         if n_slots < 1:
             raise ValueError(f"n_slots must be >= 1 (got {n_slots})")
+        # kv_pages > 0: the cache is a pool of kv_pages pages of page_size
+        # rows and every slot reaches its rows through a page table
+        # (set_slot_pages); n_slots then sizes the table, not the memory
+        self.kv_pages = kv_pages
+        self.page_size = page_size
+        self.page_map = None
+        if kv_pages:
+            from .rows import PageMap
+            self.page_map = PageMap(n_slots, config.seq_len, kv_pages,
+                                    page_size)
         # KV slots: n_slots sequences of seq_len cache rows each; forward
         # lives in slot 0, forward_rows addresses any of them
         self.n_slots = n_slots
@@ -108,8 +119,25 @@ class CpuTransformer:
             self.layers.append(lw)
 
         self.rope = R.rope_cache(c.seq_len, c.head_dim, c.rope_theta, c.rope_scaling)
-        self.k_cache = torch.zeros(c.n_layers, n_slots * c.seq_len, c.kv_dim0)
-        self.v_cache = torch.zeros(c.n_layers, n_slots * c.seq_len, c.kv_dim0)
+        kv_rows = kv_pages * page_size if kv_pages else n_slots * c.seq_len
+        self.k_cache = torch.zeros(c.n_layers, kv_rows, c.kv_dim0)
+        self.v_cache = torch.zeros(c.n_layers, kv_rows, c.kv_dim0)
+
+    # ------------------------------------------------------------ pages
+
+    def set_slot_pages(self, slot: int, pages, first: int = 0) -> None:
+        """Paged model: map pool pages into the slot's page table from page
+        index `first`. ValueError for an id outside 0..kv_pages-1."""
+        self._paged().set_slot_pages(slot, pages, first)
+
+    def clear_slot(self, slot: int) -> None:
+        """Paged model: unmap every page of the slot."""
+        self._paged().clear_slot(slot)
+
+    def _paged(self):
+        if self.page_map is None:
+            raise ValueError("the model has no paged KV cache (kv_pages=0)")
+        return self.page_map
 
     # ------------------------------------------------------------------
 
@@ -140,6 +168,10 @@ class CpuTransformer:
 
     def forward(self, tokens: torch.Tensor, positions: torch.Tensor) -> torch.Tensor:
         """tokens, positions: int64 [B] -> logits f32 [B, vocab] (all ranks)."""
+        if self.page_map is not None:
+            raise ValueError(
+                "a paged model steps rows only (forward_rows); one sequence "
+                "runs on the unpaged default")
         if int(positions[-1]) >= self.cfg.seq_len:
             raise ValueError(
                 f"position {int(positions[-1])} exceeds seq_len "
@@ -151,24 +183,43 @@ class CpuTransformer:
         sequence in KV slot slots[b] -> logits f32 [B, vocab]. Decode rows
         of different sequences, prompt chunks, or both; rows of one slot see
         each other's K/V. ValueError for a slot >= n_slots, a position >=
-        seq_len, a repeated (slot, position) or more than n_batches rows."""
+        seq_len, a repeated (slot, position) or more than n_batches rows;
+        on a paged model also for a position in or above an unmapped page
+        and for a write into a page that several slots map."""
         from .rows import check_rows
         c = self.cfg
         tokens, slots, positions = check_rows(
             tokens, slots, positions, self.n_slots, c.seq_len, self.n_batches)
+        if self.page_map is not None:
+            self.page_map.check(slots, positions)
+            self.page_map.dirty.clear()  # the gathers read the map itself
+            return self._step(torch.tensor(tokens, dtype=torch.int64),
+                              torch.tensor(positions, dtype=torch.int64),
+                              None, slots)
         return self._step(torch.tensor(tokens, dtype=torch.int64),
                           torch.tensor(positions, dtype=torch.int64),
                           [s * c.seq_len for s in slots])
 
     def _step(self, tokens: torch.Tensor, positions: torch.Tensor,
-              bases: list | None) -> torch.Tensor:
+              bases: list | None, paged_slots: list | None = None) -> torch.Tensor:
         """The layer stream over B rows. bases: every row's first cache row
-        (slot * seq_len); None = all rows in slot 0."""
+        (slot * seq_len); None = all rows in slot 0. paged_slots: every
+        row's slot of a paged model, whose rows go through the page map."""
         c = self.cfg
         B = tokens.shape[0]
         cache_rows = positions.long()
         if bases is not None:
             cache_rows = cache_rows + torch.tensor(bases, dtype=torch.int64)
+        if paged_slots is not None:
+            pm = self.page_map
+            cache_rows = torch.tensor(
+                [pm.cache_row(s, int(p)) for s, p in zip(paged_slots, positions)],
+                dtype=torch.int64)
+            # per row: the pool rows of positions 0..pos, in position order
+            gathers = [torch.tensor([pm.cache_row(s, t)
+                                     for t in range(int(p) + 1)],
+                                    dtype=torch.int64)
+                       for s, p in zip(paged_slots, positions)]
         x = self.embedding[tokens.long()].clone()  # [B, dim], replicated
 
         for l, lw in enumerate(self.layers):
@@ -185,7 +236,14 @@ class CpuTransformer:
             k = self._rope(k, positions)
             self.k_cache[l, cache_rows] = k
             self.v_cache[l, cache_rows] = v
-            if bases is None:
+            if paged_slots is not None:
+                # the unpaged branch below on rows gathered through the map
+                z = torch.cat([
+                    R.attention(q[b:b + 1], self.k_cache[l, rows],
+                                self.v_cache[l, rows], positions[b:b + 1],
+                                c.n_heads0, c.head_dim)
+                    for b, rows in enumerate(gathers)])
+            elif bases is None:
                 z = R.attention(q, self.k_cache[l], self.v_cache[l], positions,
                                 c.n_heads0, c.head_dim)
             else:

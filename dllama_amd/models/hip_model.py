@@ -26,7 +26,9 @@ A fourth schedule, `_forward_rows_buffers`, steps rows of several sequences
 together: the KV cache holds `n_slots` sequences and a per-row {cache row
 base, position} table replaces "row b is position pos+b" in rope, KV write
 and attention (`forward_rows`, docs/DESIGN.md §8). With the default of one
-slot nothing of it is allocated or launched.
+slot nothing of it is allocated or launched. With `kv_pages > 0` the same
+schedule runs the paged forms of those three kernels: the cache is a pool of
+pages and each slot reaches its rows through a device page table.
 """
 
 from __future__ import annotations
@@ -115,7 +117,7 @@ class HipTransformer:
 
     def __init__(self, config: ModelConfig, device=None, comm: Comm | None = None,
                  n_batches: int = 32, force_sync: bool = False,
-                 n_slots: int = 1):
+                 n_slots: int = 1, kv_pages: int = 0, page_size: int = 64):
         self.cfg = c = config
         # KV slots: each layer's cache holds n_slots sequences of seq_len
         # rows; every single-sequence path lives in slot 0 (the first
@@ -123,6 +125,17 @@ class HipTransformer:
         if n_slots < 1:
             raise ValueError(f"n_slots must be >= 1 (got {n_slots})")
         self.n_slots = n_slots
+        # kv_pages > 0: each layer's cache is a pool of kv_pages pages of
+        # page_size rows, and a slot reaches its rows through a page table
+        # (set_slot_pages); n_slots then sizes the table, not the memory.
+        # A paged model steps rows only.
+        self.kv_pages = kv_pages
+        self.page_size = page_size
+        self.page_map = None
+        self.page_table_sends = 0  # copies of table rows to the device
+        if kv_pages:
+            from .rows import PageMap
+            self.page_map = PageMap(n_slots, c.seq_len, kv_pages, page_size)
         self.comm = comm or SingleComm()
         # force_sync: run the full TP sync/gather/concat path at world=1
         # (SingleComm collectives are identity) — lets a 1-GPU box validate
@@ -213,14 +226,16 @@ class HipTransformer:
     def from_file(cls, m: ModelFile, config: ModelConfig, device=None,
                   comm: Comm | None = None, n_batches: int = 32,
                   force_sync: bool = False,
-                  n_slots: int = 1) -> "HipTransformer":
+                  n_slots: int = 1, kv_pages: int = 0,
+                  page_size: int = 64) -> "HipTransformer":
         from ..quants import Q40
         if m.header.weight_type != Q40:
             raise ValueError(
                 "the MI355X HIP backend runs Q40 weights (the reference's "
                 "shipped format); f32/q80 .m files run on the CPU backend "
                 "(--gpu-index -1) or can be re-quantized with convert_hf.py")
-        self = cls(config, device, comm, n_batches, force_sync, n_slots)
+        self = cls(config, device, comm, n_batches, force_sync, n_slots,
+                   kv_pages, page_size)
         c, dev = config, self.device
         r, w = c.rank, c.world
 
@@ -271,10 +286,12 @@ class HipTransformer:
     def synthetic(cls, config: ModelConfig, device=None, comm: Comm | None = None,
                   n_batches: int = 32, seed: int = 1234,
                   force_sync: bool = False,
-                  n_slots: int = 1) -> "HipTransformer":
+                  n_slots: int = 1, kv_pages: int = 0,
+                  page_size: int = 64) -> "HipTransformer":
         """Random-init weights built directly on device (benches: no network
         for checkpoints, and an 8B .m file round-trip is pointless there)."""
-        self = cls(config, device, comm, n_batches, force_sync, n_slots)
+        self = cls(config, device, comm, n_batches, force_sync, n_slots,
+                   kv_pages, page_size)
         c, dev = config, self.device
         gen = torch.Generator(device=dev)
         gen.manual_seed(seed + c.rank)
@@ -403,6 +420,12 @@ class HipTransformer:
         self.rope_cache = cache.reshape(c.seq_len, c.head_dim).contiguous().to(dev)
         kv_dt = torch.float32 if self.kv_f32 else torch.float16
         kv_rows = self.n_slots * c.seq_len  # slot s = rows s*seq_len ...
+        if self.page_map is not None:
+            kv_rows = self.kv_pages * self.page_size
+            # unmapped entries hold 0: the table never points outside the pool
+            self.page_table = torch.zeros(
+                self.n_slots, self.page_map.pages_per_seq, dtype=torch.int32,
+                device=dev)
         self.k_cache = [torch.zeros(kv_rows, c.kv_dim0, dtype=kv_dt, device=dev)
                         for _ in range(c.n_layers)]
         self.v_cache = [torch.zeros(kv_rows, c.kv_dim0, dtype=kv_dt, device=dev)
@@ -465,11 +488,14 @@ class HipTransformer:
         """_qknorm_rope_kv with every row's rope position and cache row
         taken from the row table."""
         c, k = self.cfg, self.k
+        paged = self.page_map is not None
+        pt = (self.page_table, self.page_size) if paged else ()
         if c.is_qwen3 and self.rope_style == 1:
-            k.rope_kv_qknorm_rows(self.qkv_out, self.qkv_ld, c.q_dim0,
-                                  c.kv_dim0, self.rope_cache, self.rows,
-                                  self.k_cache[l], self.v_cache[l], c.head_dim,
-                                  lw["q_norm"], lw["k_norm"], c.norm_eps, B)
+            op = k.rope_kv_qknorm_paged if paged else k.rope_kv_qknorm_rows
+            op(self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0,
+               self.rope_cache, self.rows, *pt, self.k_cache[l],
+               self.v_cache[l], c.head_dim, lw["q_norm"], lw["k_norm"],
+               c.norm_eps, B)
             return
         if c.is_qwen3:
             for col0, width, wn in ((0, c.q_dim0, lw["q_norm"]),
@@ -477,14 +503,22 @@ class HipTransformer:
                 k.rmsnorm_rows_s(self.qkv_out, self.qkv_ld, col0,
                                  width // c.head_dim, B, wn, c.head_dim,
                                  c.norm_eps)
-        k.rope_kv_rows(self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0,
-                       self.rope_cache, self.rows, self.k_cache[l],
-                       self.v_cache[l], c.head_dim, self.rope_style, B)
+        op = k.rope_kv_paged if paged else k.rope_kv_rows
+        op(self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0, self.rope_cache,
+           self.rows, *pt, self.k_cache[l], self.v_cache[l], c.head_dim,
+           self.rope_style, B)
 
     def _attn_rows(self, l: int, B: int):
         """Attention of every row over its own slot's rows of layer l's
         cache, into the Q80 triple zq that the wo matmul consumes."""
         c = self.cfg
+        if self.page_map is not None:
+            self.k.attn_paged(self.qkv_out, self.qkv_ld, self.k_cache[l],
+                              self.v_cache[l], self.zbuf[:B], self.rows,
+                              self.page_table, self.page_size, B, c.n_heads0,
+                              self.kv_mul, c.head_dim, self.attn_splits,
+                              self.attn_ml, self.attn_o, *self.zq.triple())
+            return
         self.k.attn_rows(self.qkv_out, self.qkv_ld, self.k_cache[l],
                          self.v_cache[l], self.zbuf[:B], self.rows, B,
                          c.n_heads0, self.kv_mul, c.head_dim, self.attn_splits,
@@ -824,6 +858,7 @@ class HipTransformer:
 
         When a decode graph is captured and B==1, this is a single hipGraph
         replay (the graph advances the device position itself)."""
+        self._rows_only()
         B = tokens.shape[0]
         assert B <= self.n_batches
         p0 = int(positions[0])
@@ -902,6 +937,7 @@ class HipTransformer:
         launches). Only the token id and the parameters go to the device and
         {token, status} comes back; the logits stay in place (last_logits),
         so a None result can be resampled by the caller."""
+        self._rows_only()
         assert tokens.shape[0] == 1
         p0 = int(positions[0])
         if p0 + 1 > self.cfg.seq_len:
@@ -925,6 +961,41 @@ class HipTransformer:
             self.forward_buffers(1)
             smp.launch(self.last_logits())
         return smp.read()
+
+    # ------------------------------------------------------------ pages
+
+    def _rows_only(self):
+        if self.page_map is not None:
+            raise ValueError(
+                "a paged model steps rows only (forward_rows); one sequence "
+                "runs on the unpaged default")
+
+    def _paged(self):
+        if self.page_map is None:
+            raise ValueError("the model has no paged KV cache (kv_pages=0)")
+        return self.page_map
+
+    def set_slot_pages(self, slot: int, pages, first: int = 0) -> None:
+        """Paged model: map pool pages into the slot's page table from page
+        index `first`. ValueError for an id outside 0..kv_pages-1. The
+        device table follows before the next row step."""
+        self._paged().set_slot_pages(slot, pages, first)
+
+    def clear_slot(self, slot: int) -> None:
+        """Paged model: unmap every page of the slot."""
+        self._paged().clear_slot(slot)
+
+    def _send_page_table(self):
+        """Copy the table rows of the slots whose mapping changed, on the
+        current stream: ordered after the steps already queued and before
+        the next one, a replayed row graph included. Nothing to send in
+        steady decode."""
+        pm = self.page_map
+        for slot in sorted(pm.dirty):
+            self.page_table[slot].copy_(
+                torch.tensor(pm.device_row(slot), dtype=torch.int32))
+            self.page_table_sends += 1
+        pm.dirty.clear()
 
     # ------------------------------------------------------------ row steps
 
@@ -974,11 +1045,16 @@ class HipTransformer:
         tokens, slots, positions = check_rows(
             tokens, slots, positions, self.n_slots, c.seq_len, NB)
         B = len(tokens)
+        stride = c.seq_len  # word 0 of a table row: the slot's first cache row
+        if self.page_map is not None:
+            self.page_map.check(slots, positions)
+            self._send_page_table()
+            stride = self.page_map.pages_per_seq  # ... or its page table row
         self._rows_buffers()
         if self._rows_copied is not None:
             self._rows_copied.synchronize()  # the host twin is free again
         host = self._rows_host
-        table = [(s * c.seq_len, p) for s, p in zip(slots, positions)]
+        table = [(s * stride, p) for s, p in zip(slots, positions)]
         host[:NB] = 0
         host[:B] = torch.tensor(tokens, dtype=torch.int64)
         hp = host[NB:5 * NB].view(torch.float64).view(NB, 4)
@@ -1088,7 +1164,9 @@ class HipTransformer:
         decode rows of different sequences, prompt chunks (several rows of
         one slot at consecutive positions), or both. ValueError, before any
         launch, for a slot >= n_slots, a position >= seq_len, a repeated
-        (slot, position) or more than n_batches rows."""
+        (slot, position) or more than n_batches rows; on a paged model also
+        for a position in or above an unmapped page of its slot, and for a
+        row that would write into a page several table entries name."""
         B, table, decode_only = self._stage_rows(tokens, slots, positions)
         self._run_rows(B, table, decode_only, sample=False)
         return self.rows_logits(B)
@@ -1185,6 +1263,7 @@ class HipTransformer:
         (the HIP analog of the reference's recorded Vulkan command buffers,
         nn-vulkan.cpp:1065-1118). With device_sampling the temperature/top-p
         sampler runs inside it, between the step and the pos advance."""
+        self._rows_only()
         sample = bool(self.device_sampling)
         self._graph = self._warm_and_capture(1, warmups=2, advance_pos=True,
                                              sample=sample)

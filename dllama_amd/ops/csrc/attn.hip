@@ -5,23 +5,50 @@
 // ------------------------------------------------- row addressing policies
 // Which sequence position a batch row is, and where its sequence starts in
 // the KV cache. The positional kernels below are templated on one of these;
-// both read wave-uniform values (b is a blockIdx), so they stay scalar.
+// all read wave-uniform values (b is a blockIdx), so they stay scalar.
 //
 // SeqRows: row b is position pos[0]+b of the one cache (a prompt chunk or a
 // decode step of a single sequence).
+//
+// cache_row(b, t) is the cache row of position t of row b's sequence. The
+// first two policies keep a sequence in consecutive rows, so attention takes
+// cache_base(b) once and adds t itself; PagedRows looks t up per page.
 struct SeqRows {
+    static constexpr bool kPaged = false;
     const int *pos;
     __device__ int position(int b) const { return pos[0] + b; }
     __device__ int64_t cache_base(int) const { return 0; }
+    __device__ int64_t cache_row(int, int t) const { return t; }
 };
 // TableRows: int32 [B, 2] = {cache_row_base, pos} per row, cache_row_base =
 // slot * seq_len: row b is position pos of the sequence whose cache rows
 // start at cache_row_base. Expresses N sequences decoding together, a prompt
 // chunk into any slot, and any mix of the two.
 struct TableRows {
+    static constexpr bool kPaged = false;
     const int *rows;
     __device__ int position(int b) const { return rows[2 * b + 1]; }
     __device__ int64_t cache_base(int b) const { return rows[2 * b]; }
+    __device__ int64_t cache_row(int b, int t) const {
+        return (int64_t)rows[2 * b] + t;
+    }
+};
+// PagedRows: the same [B, 2] table, word 0 now the row's offset into a page
+// table (slot * pages_per_seq). The cache is a pool of pages of P = 1<<shift
+// rows; position t of row b lives in row pages[offset + t/P] * P + t%P.
+struct PagedRows {
+    static constexpr bool kPaged = true;
+    const int *rows;
+    const int *pages;
+    int shift;
+    __device__ int position(int b) const { return rows[2 * b + 1]; }
+    __device__ int64_t cache_base(int) const { return 0; }
+    // the page ids of row b's sequence, by page index
+    __device__ const int *seq_pages(int b) const { return pages + rows[2 * b]; }
+    __device__ int64_t cache_row(int b, int t) const {
+        return ((int64_t)seq_pages(b)[t >> shift] << shift)
+             + (t & ((1 << shift) - 1));
+    }
 };
 
 // ------------------------------------------------- split-K flash decode
@@ -51,7 +78,11 @@ __global__ void k_attn_split(const float *__restrict__ q, int q_ld,
     const int plen = rows.position(b) + 1;
     const KVT *kc = kc_all + rows.cache_base(b) * kv_dim0;
     const KVT *vc = vc_all + rows.cache_base(b) * kv_dim0;
-    const int wave = threadIdx.x / WAVE;
+    // paged: the wave index made provably uniform, so the page-id loads
+    // below are scalar loads beside the vector K/V stream
+    const int wave = ROWS::kPaged
+        ? __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE)
+        : threadIdx.x / WAVE;
     const int lane = threadIdx.x % WAVE;
     const int kv_off = (h0 / kv_mul) * hd;
 
@@ -76,14 +107,47 @@ __global__ void k_attn_split(const float *__restrict__ q, int q_ld,
     // serializing behind the softmax chain (the 1-chunk-per-round loop was
     // latency-bound: ~13 us at pos 1024 for ~1.3 us of KV traffic)
     const int stride = 16 * S;
+    // Paged: chunk u of a round covers t = tb0 + u*stride + 0..3, which
+    // starts at a multiple of 4 and so lies in one page for every P >= 4: one
+    // page id per chunk, four per round. They are loaded a round ahead, all
+    // four together (this round's arrive while the previous round's K/V
+    // stream), so the lookup adds no serial hop in front of the K loads. A
+    // chunk at or past plen reads no id: its entry may be past the table.
+    [[maybe_unused]] int pg[4];
+    [[maybe_unused]] const int *seq_pages = nullptr;
+    [[maybe_unused]] int pshift = 0;
+    if constexpr (ROWS::kPaged) {
+        seq_pages = rows.seq_pages(b);
+        pshift = rows.shift;
+        #pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int t = (sp * 4 + wave) * 4 + u * stride;
+            pg[u] = t < plen ? seq_pages[t >> pshift] : 0;
+        }
+    }
     for (int tb0 = (sp * 4 + wave) * 4; tb0 < plen; tb0 += 4 * stride) {
+        // paged: first cache row of each chunk
+        [[maybe_unused]] int64_t rb[4];
+        if constexpr (ROWS::kPaged) {
+            #pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int t = tb0 + u * stride;
+                rb[u] = ((int64_t)pg[u] << pshift) + (t & ((1 << pshift) - 1));
+            }
+            #pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int t = tb0 + 4 * stride + u * stride;
+                pg[u] = t < plen ? seq_pages[t >> pshift] : 0;
+            }
+        }
         float su[4];
         #pragma unroll
         for (int u = 0; u < 4; u++) {
             const int tg = tb0 + u * stride + group;
             float partial = 0.0f;
             if (tg < plen) {
-                const KVT *krow = kc + (int64_t)tg * kv_dim0 + kv_off + lane16 * VEC16;
+                const int64_t kr = ROWS::kPaged ? rb[u] + group : (int64_t)tg;
+                const KVT *krow = kc + kr * kv_dim0 + kv_off + lane16 * VEC16;
                 #pragma unroll
                 for (int v = 0; v < VEC16; v++)
                     partial = fmaf(qreg[v], kv_f(krow[v]), partial);
@@ -119,7 +183,8 @@ __global__ void k_attn_split(const float *__restrict__ q, int q_ld,
             for (int gg = 0; gg < 4; gg++) {
                 const int t = tb0 + u * stride + gg;
                 if (t >= plen) continue;
-                const KVT *vrow = vc + (int64_t)t * kv_dim0 + kv_off + lane * VEC;
+                const int64_t vr = ROWS::kPaged ? rb[u] + gg : (int64_t)t;
+                const KVT *vrow = vc + vr * kv_dim0 + kv_off + lane * VEC;
                 #pragma unroll
                 for (int v = 0; v < VEC; v++)
                     o[v] = fmaf(w16[4 * u + gg], kv_f(vrow[v]), o[v]);
@@ -392,7 +457,7 @@ __global__ void k_rope_kv(float *__restrict__ qkv, int ld,
                           int hd) {
     const int b = blockIdx.y;
     const int rp = rows.position(b);          // rope position
-    const int64_t p = rows.cache_base(b) + rp;  // cache row written
+    const int64_t p = rows.cache_row(b, rp);  // cache row written
     const int half = hd >> 1;
     const float *pc = cache + (int64_t)rp * hd;
     float *qrow = qkv + (int64_t)b * ld;
@@ -467,7 +532,7 @@ __global__ void k_rope_kv_qknorm(float *__restrict__ qkv, int ld,
                                  const float *__restrict__ wk, float eps) {
     const int b = blockIdx.y;
     const int rp = rows.position(b);          // rope position
-    const int64_t p = rows.cache_base(b) + rp;  // cache row written
+    const int64_t p = rows.cache_row(b, rp);  // cache row written
     const int h = blockIdx.x;
     const int qh = q_dim0 / hd, kvh = kv_dim0 / hd;
     const int half = hd >> 1;
@@ -579,7 +644,34 @@ static TableRows table_rows(const torch::Tensor &rows, int64_t batch) {
     return TableRows{rows.data_ptr<int>()};
 }
 
-// Split + combine launches of attention, for either row addressing. The
+// The paged form of a row table: word 0 of a row indexes page_table (int32
+// [n_slots, pages_per_seq], contiguous, on the cache's device), whose
+// entries are page ids of a cache of whole pages of page_size rows. The
+// contents of both tables are the caller's to validate.
+static PagedRows paged_rows(const torch::Tensor &rows,
+                            const torch::Tensor &page_table, int64_t page_size,
+                            int64_t batch, const torch::Tensor &kc) {
+    const TableRows t = table_rows(rows, batch);
+    CHECK_CUDA(page_table);
+    TORCH_CHECK(page_table.scalar_type() == at::kInt && page_table.dim() == 2
+                && page_table.is_contiguous() && page_table.numel() > 0
+                && page_table.device() == kc.device()
+                && rows.device() == kc.device(),
+                "page table must be a contiguous int32 [n_slots, "
+                "pages_per_seq] on the cache's device");
+    TORCH_CHECK(page_size >= 4 && page_size <= 256
+                && (page_size & (page_size - 1)) == 0,
+                "page_size must be a power of two in 4..256 (got ",
+                page_size, ")");
+    TORCH_CHECK(kc.size(0) % page_size == 0,
+                "a paged cache holds whole pages: ", kc.size(0),
+                " rows, page_size ", page_size);
+    int shift = 0;
+    while ((int64_t(1) << shift) < page_size) shift++;
+    return PagedRows{t.rows, page_table.data_ptr<int>(), shift};
+}
+
+// Split + combine launches of attention, for any row addressing. The
 // GQA-grouped experiment and the S==1 fused kernel (allow_variants) exist
 // for the single-sequence form only.
 template <typename ROWS>
@@ -690,6 +782,22 @@ void attn_rows(torch::Tensor q, int64_t q_ld, torch::Tensor kc, torch::Tensor vc
                 false, zq, zs, zbs);
 }
 
+// attn_rows over a paged cache: row b attends over positions 0..pos_b of its
+// sequence, each found through the page table.
+void attn_paged(torch::Tensor q, int64_t q_ld, torch::Tensor kc, torch::Tensor vc,
+                torch::Tensor y, torch::Tensor rows, torch::Tensor page_table,
+                int64_t page_size, int64_t batch, int64_t n_heads0,
+                int64_t kv_mul, int64_t head_dim, int64_t splits,
+                torch::Tensor ml_scratch, torch::Tensor o_scratch,
+                c10::optional<torch::Tensor> zq = c10::nullopt,
+                c10::optional<torch::Tensor> zs = c10::nullopt,
+                c10::optional<torch::Tensor> zbs = c10::nullopt) {
+    attn_launch(q, q_ld, kc, vc, y,
+                paged_rows(rows, page_table, page_size, batch, kc), batch,
+                n_heads0, kv_mul, head_dim, splits, ml_scratch, o_scratch,
+                nullptr, false, zq, zs, zbs);
+}
+
 template <typename ROWS>
 static void rope_kv_launch(torch::Tensor &qkv, int64_t ld, int64_t q_dim0,
                            int64_t kv_dim0, torch::Tensor &cache, ROWS rows,
@@ -721,6 +829,16 @@ void rope_kv_rows(torch::Tensor qkv, int64_t ld, int64_t q_dim0, int64_t kv_dim0
                   int64_t batch) {
     rope_kv_launch(qkv, ld, q_dim0, kv_dim0, cache, table_rows(rows, batch),
                    kc, vc, head_dim, style, batch);
+}
+
+void rope_kv_paged(torch::Tensor qkv, int64_t ld, int64_t q_dim0, int64_t kv_dim0,
+                   torch::Tensor cache, torch::Tensor rows,
+                   torch::Tensor page_table, int64_t page_size,
+                   torch::Tensor kc, torch::Tensor vc, int64_t head_dim,
+                   int64_t style, int64_t batch) {
+    rope_kv_launch(qkv, ld, q_dim0, kv_dim0, cache,
+                   paged_rows(rows, page_table, page_size, batch, kc), kc, vc,
+                   head_dim, style, batch);
 }
 
 template <typename ROWS>
@@ -764,6 +882,17 @@ void rope_kv_qknorm_rows(torch::Tensor qkv, int64_t ld, int64_t q_dim0,
                           eps, batch);
 }
 
+void rope_kv_qknorm_paged(torch::Tensor qkv, int64_t ld, int64_t q_dim0,
+                          int64_t kv_dim0, torch::Tensor cache,
+                          torch::Tensor rows, torch::Tensor page_table,
+                          int64_t page_size, torch::Tensor kc,
+                          torch::Tensor vc, int64_t head_dim, torch::Tensor wq,
+                          torch::Tensor wk, double eps, int64_t batch) {
+    rope_kv_qknorm_launch(qkv, ld, q_dim0, kv_dim0, cache,
+                          paged_rows(rows, page_table, page_size, batch, kc),
+                          kc, vc, head_dim, wq, wk, eps, batch);
+}
+
 // pos += 1 in the first `batch` rows of a row table: a captured all-decode
 // step advances itself, as pos_inc does for the single sequence
 void rows_advance(torch::Tensor rows, int64_t batch) {
@@ -782,6 +911,15 @@ void register_attn(py::module &m) {
     m.def("rows_advance", &rows_advance);
     m.def("attn_rows", &attn_rows, py::arg("q"), py::arg("q_ld"), py::arg("kc"),
           py::arg("vc"), py::arg("y"), py::arg("rows"), py::arg("batch"),
+          py::arg("n_heads0"), py::arg("kv_mul"), py::arg("head_dim"),
+          py::arg("splits"), py::arg("ml_scratch"), py::arg("o_scratch"),
+          py::arg("zq") = py::none(), py::arg("zs") = py::none(),
+          py::arg("zbs") = py::none());
+    m.def("rope_kv_paged", &rope_kv_paged);
+    m.def("rope_kv_qknorm_paged", &rope_kv_qknorm_paged);
+    m.def("attn_paged", &attn_paged, py::arg("q"), py::arg("q_ld"),
+          py::arg("kc"), py::arg("vc"), py::arg("y"), py::arg("rows"),
+          py::arg("page_table"), py::arg("page_size"), py::arg("batch"),
           py::arg("n_heads0"), py::arg("kv_mul"), py::arg("head_dim"),
           py::arg("splits"), py::arg("ml_scratch"), py::arg("o_scratch"),
           py::arg("zq") = py::none(), py::arg("zs") = py::none(),

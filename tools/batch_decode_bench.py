@@ -11,11 +11,21 @@ included. The last entry is the single-sequence path (`forward_sample`
 over the deferred-quant decode graph) timed the same way, the figure the
 B=1 row path is compared with.
 
+--kv-pages M runs the same loop on a paged KV cache of M pages (--page-size
+rows each): slot s takes pages s, s+B, s+2B, ... so that no sequence is
+contiguous in the pool. The single-sequence entry is left out then (a paged
+model steps rows only). --context N starts the timed decode at position N:
+the prompt is still --prefill tokens, the cache rows between hold zeros, and
+every step reads all N of them, so long contexts are timed without paying
+B long prefills.
+
 Warmup and timing follow bench.py: untimed warmup steps on the shapes of
 the timed window, then a host clock around `--steps` steps ending in a
 device synchronise. Prints one JSON line.
 
 Usage: python tools/batch_decode_bench.py [--steps 200] [--warmup 20]
+           [--batches 1,8,32] [--context 4000 --seq-len 8192]
+           [--kv-pages 4096 --page-size 64]
 """
 
 import argparse
@@ -39,7 +49,14 @@ def main():
     ap.add_argument("--prefill", type=int, default=32,
                     help="prompt tokens per sequence before the timed decode")
     ap.add_argument("--batches", default="1,2,4,8,16,32")
+    ap.add_argument("--context", type=int, default=0,
+                    help="position of the first timed decode step (default: "
+                         "--prefill); rows past the prompt hold zeros")
+    ap.add_argument("--kv-pages", type=int, default=0,
+                    help="page the KV cache: pool of this many pages")
+    ap.add_argument("--page-size", type=int, default=64)
     args = ap.parse_args()
+    context = max(args.context, args.prefill)
     if not torch.cuda.is_available():
         sys.exit("error: batch_decode_bench needs a GPU")  # no CPU fall-back
 
@@ -55,13 +72,21 @@ def main():
     header = mf.preset_header(args.model, seq_len=args.seq_len)
     cfg = ModelConfig.from_header(header)
     t0 = time.time()
-    model = HipTransformer.synthetic(cfg, device=device, n_slots=max(batches))
+    paging = (dict(kv_pages=args.kv_pages, page_size=args.page_size)
+              if args.kv_pages else {})
+    model = HipTransformer.synthetic(cfg, device=device, n_slots=max(batches),
+                                     **paging)
     model.device_sampling = True
     torch.cuda.synchronize(device)
     print(f"# built synthetic {args.model} with {model.n_slots} KV slots in "
           f"{time.time() - t0:.1f}s", file=sys.stderr)
-    if args.prefill + args.warmup + args.steps > cfg.seq_len:
-        sys.exit("error: prefill + warmup + steps exceed --seq-len")
+    last = context + args.warmup + args.steps
+    if last > cfg.seq_len:
+        sys.exit("error: context + warmup + steps exceed --seq-len")
+    pages_per_slot = -(-last // args.page_size)
+    if args.kv_pages and pages_per_slot * max(batches) > args.kv_pages:
+        sys.exit(f"error: {max(batches)} sequences of {last} positions need "
+                 f"{pages_per_slot * max(batches)} pages")
 
     torch.manual_seed(1234)
     prompt = torch.randint(0, cfg.vocab_size, (args.prefill,)).tolist()
@@ -83,12 +108,18 @@ def main():
     rows = {}
     for B in batches:
         slots = list(range(B))
+        if args.kv_pages:
+            for s in range(model.n_slots):
+                model.clear_slot(s)
+            for s in slots:  # interleaved: no sequence is contiguous
+                model.set_slot_pages(s, [i * B + s
+                                         for i in range(pages_per_slot)])
         for s in slots:  # every sequence's prompt, one chunk per step
             for i in range(0, args.prefill, model.n_batches):
                 chunk = prompt[i: i + model.n_batches]
                 model.forward_rows(chunk, [s] * len(chunk),
                                    list(range(i, i + len(chunk))))
-        state = {"tokens": [7] * B, "pos": args.prefill}
+        state = {"tokens": [7] * B, "pos": context}
         zeros, topps = [0.0] * B, [0.9] * B
 
         def step():
@@ -104,18 +135,20 @@ def main():
 
     # the single-sequence path, same loop shape: forward_sample replays the
     # deferred-quant decode graph with the sampler inside
-    model.forward(torch.tensor(prompt[: model.n_batches]),
-                  torch.arange(min(args.prefill, model.n_batches)))
-    model.capture_decode_graph()
-    state = {"token": 7, "pos": args.prefill}
+    single_entry = None
+    if not args.kv_pages:
+        model.forward(torch.tensor(prompt[: model.n_batches]),
+                      torch.arange(min(args.prefill, model.n_batches)))
+        model.capture_decode_graph()
+        state = {"token": 7, "pos": context}
 
-    def single():
-        state["token"] = model.forward_sample(
-            torch.tensor([state["token"]]), torch.tensor([state["pos"]]),
-            0.0, 0.0, 0.9)
-        state["pos"] += 1
+        def single():
+            state["token"] = model.forward_sample(
+                torch.tensor([state["token"]]), torch.tensor([state["pos"]]),
+                0.0, 0.0, 0.9)
+            state["pos"] += 1
 
-    single_entry = entry(timed(single), 1)
+        single_entry = entry(timed(single), 1)
 
     mname = "Llama-3.1-8B" if args.model == "llama-3.1-8b" else args.model
     print(json.dumps({
@@ -128,7 +161,10 @@ def main():
         "rows": rows,
         "single_stream_forward_sample": single_entry,
         "config": {"model": args.model, "seq_len": args.seq_len,
-                   "prefill": args.prefill, "n_slots": model.n_slots,
+                   "prefill": args.prefill, "context": context,
+                   "kv_pages": args.kv_pages,
+                   "page_size": args.page_size if args.kv_pages else None,
+                   "n_slots": model.n_slots,
                    "sampling": "on device, temperature 0",
                    "data": "synthetic (random-init weights, random prompt)"},
     }))
