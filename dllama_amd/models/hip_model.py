@@ -16,19 +16,24 @@ Architecture (MI355X-first):
 
 Three launch schedules share one set of stages (the `_`-prefixed methods
 under "stages": each kernel call site with its argument plumbing exists
-once): `forward_buffers` (explicit norm_quant per matmul; any batch),
+once): `_forward_explicit` (explicit norm_quant per matmul; any batch),
 `_forward_dense_deferred` (B=1 decode, quantization deferred into the
 producers' epilogues) and `_forward_prefill_bf16` (library bf16 GEMMs, an
-A/B baseline). tests/test_launch_trace.py pins the resulting launch
-sequences.
+A/B baseline). `forward_buffers` picks among them for a single-sequence
+step. tests/test_launch_trace.py pins the resulting launch sequences.
 
-A fourth schedule, `_forward_rows_buffers`, steps rows of several sequences
-together: the KV cache holds `n_slots` sequences and a per-row {cache row
-base, position} table replaces "row b is position pos+b" in rope, KV write
-and attention (`forward_rows`, docs/DESIGN.md §8). With the default of one
-slot nothing of it is allocated or launched. With `kv_pages > 0` the same
-schedule runs the paged forms of those three kernels: the cache is a pool of
-pages and each slot reaches its rows through a device page table.
+Rope, KV write and attention reach a row's position and cache rows through
+a `KVAddr`. The single-sequence value says "row b is position pos+b of slot
+0". A row step (`forward_rows`, docs/DESIGN.md §8) runs the explicit-norm
+schedule with the row-table value instead: the KV cache holds `n_slots`
+sequences and a per-row {cache row base, position} table places each row,
+so one step carries rows of several sequences. With `kv_pages > 0` the
+value also names a device page table: the cache is a pool of pages and each
+slot reaches its rows through it. With the default of one slot nothing of
+this is allocated or launched.
+
+Whatever is captured as a hipGraph (the decode step, a full prefill chunk,
+an all-decode row step) goes through one procedure, `_capture`.
 """
 
 from __future__ import annotations
@@ -108,6 +113,30 @@ def _pow2_batch(b: int) -> int:
     while nb < b:
         nb *= 2
     return nb
+
+
+class KVAddr:
+    """How the positional kernels (rope, KV write, attention) find batch row
+    b's position and its sequence's cache rows. Three values exist:
+
+      KVAddr("", pos, attn_scratch=(attn_counter,))
+          one sequence: row b is position pos[0]+b of slot 0;
+      KVAddr("_rows", rows)
+          the row table {cache row base, position} per row;
+      KVAddr("_paged", rows, page_table, page_size)
+          the row table {page table offset, position} plus the page table.
+
+    The suffix picks the binding family, which takes `where` in the place
+    where the single-sequence bindings take `pos`; only the single-sequence
+    attention has scratch of its own to pass."""
+
+    def __init__(self, suffix: str, *where, attn_scratch=()):
+        self.rope_kv = "rope_kv" + suffix
+        self.rope_kv_qknorm = "rope_kv_qknorm" + suffix
+        self.attn = "attn" + suffix
+        self.where = where
+        self.attn_scratch = attn_scratch
+        self.row_table = bool(suffix)  # a row step, not pos..pos+B-1
 
 
 class HipTransformer:
@@ -352,6 +381,7 @@ class HipTransformer:
         self.amax_scratch = torch.zeros(self.amax_blocks, dtype=torch.int64, device=dev)
         self._alloc_attn_scratch()
         self.attn_counter = torch.zeros(NB * c.n_heads0, dtype=torch.int32, device=dev)
+        self.seq_addr = KVAddr("", self.pos, attn_scratch=(self.attn_counter,))
         if self.tp_path:
             # per-batch-size contiguous gather buffers: collectives need a
             # flat contiguous output (world, nb*...) — a [:, :nb] slice is not
@@ -462,17 +492,18 @@ class HipTransformer:
                              self.k_cache[l], self.v_cache[l], c.q_dim0,
                              c.kv_dim0, c.head_dim, **deferred)
 
-    def _qknorm_rope_kv(self, l: int, lw: dict, B: int):
+    def _qknorm_rope_kv(self, l: int, lw: dict, B: int, addr: KVAddr):
         """Per-head q/k rmsnorm (qwen3), rope and KV write on qkv_out, for
         the schedules whose QKV matmul has no rope epilogue."""
         c, k = self.cfg, self.k
         if c.is_qwen3 and self.rope_style == 1:
             # one launch (replaces 2x rmsnorm_rows_s + rope_kv = ~9 us/layer
             # of launch overhead in the captured graph)
-            k.rope_kv_qknorm(self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0,
-                             self.rope_cache, self.pos, self.k_cache[l],
-                             self.v_cache[l], c.head_dim, lw["q_norm"],
-                             lw["k_norm"], c.norm_eps, B)
+            getattr(k, addr.rope_kv_qknorm)(
+                self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0,
+                self.rope_cache, *addr.where, self.k_cache[l],
+                self.v_cache[l], c.head_dim, lw["q_norm"], lw["k_norm"],
+                c.norm_eps, B)
             return
         if c.is_qwen3:
             for col0, width, wn in ((0, c.q_dim0, lw["q_norm"]),
@@ -480,58 +511,21 @@ class HipTransformer:
                 k.rmsnorm_rows_s(self.qkv_out, self.qkv_ld, col0,
                                  width // c.head_dim, B, wn, c.head_dim,
                                  c.norm_eps)
-        k.rope_kv(self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0,
-                  self.rope_cache, self.pos, self.k_cache[l], self.v_cache[l],
-                  c.head_dim, self.rope_style, B)
+        getattr(k, addr.rope_kv)(
+            self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0, self.rope_cache,
+            *addr.where, self.k_cache[l], self.v_cache[l], c.head_dim,
+            self.rope_style, B)
 
-    def _rope_kv_rows(self, l: int, lw: dict, B: int):
-        """_qknorm_rope_kv with every row's rope position and cache row
-        taken from the row table."""
-        c, k = self.cfg, self.k
-        paged = self.page_map is not None
-        pt = (self.page_table, self.page_size) if paged else ()
-        if c.is_qwen3 and self.rope_style == 1:
-            op = k.rope_kv_qknorm_paged if paged else k.rope_kv_qknorm_rows
-            op(self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0,
-               self.rope_cache, self.rows, *pt, self.k_cache[l],
-               self.v_cache[l], c.head_dim, lw["q_norm"], lw["k_norm"],
-               c.norm_eps, B)
-            return
-        if c.is_qwen3:
-            for col0, width, wn in ((0, c.q_dim0, lw["q_norm"]),
-                                    (c.q_dim0, c.kv_dim0, lw["k_norm"])):
-                k.rmsnorm_rows_s(self.qkv_out, self.qkv_ld, col0,
-                                 width // c.head_dim, B, wn, c.head_dim,
-                                 c.norm_eps)
-        op = k.rope_kv_paged if paged else k.rope_kv_rows
-        op(self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0, self.rope_cache,
-           self.rows, *pt, self.k_cache[l], self.v_cache[l], c.head_dim,
-           self.rope_style, B)
-
-    def _attn_rows(self, l: int, B: int):
-        """Attention of every row over its own slot's rows of layer l's
-        cache, into the Q80 triple zq that the wo matmul consumes."""
+    def _attn(self, l: int, B: int, addr: KVAddr, emit_q80: bool = True):
+        """Attention of every row over its sequence's rows of layer l's
+        cache into zbuf[:B]; emit_q80 also writes the Q80 triple zq that the
+        wo matmul consumes."""
         c = self.cfg
-        if self.page_map is not None:
-            self.k.attn_paged(self.qkv_out, self.qkv_ld, self.k_cache[l],
-                              self.v_cache[l], self.zbuf[:B], self.rows,
-                              self.page_table, self.page_size, B, c.n_heads0,
-                              self.kv_mul, c.head_dim, self.attn_splits,
-                              self.attn_ml, self.attn_o, *self.zq.triple())
-            return
-        self.k.attn_rows(self.qkv_out, self.qkv_ld, self.k_cache[l],
-                         self.v_cache[l], self.zbuf[:B], self.rows, B,
-                         c.n_heads0, self.kv_mul, c.head_dim, self.attn_splits,
-                         self.attn_ml, self.attn_o, *self.zq.triple())
-
-    def _attn(self, l: int, B: int, emit_q80: bool = True):
-        """Attention over layer l's cache into zbuf[:B]; emit_q80 also
-        writes the Q80 triple zq that the wo matmul consumes."""
-        c = self.cfg
-        self.k.attn(self.qkv_out, self.qkv_ld, self.k_cache[l], self.v_cache[l],
-                    self.zbuf[:B], self.pos, B, c.n_heads0, self.kv_mul,
-                    c.head_dim, self.attn_splits, self.attn_ml, self.attn_o,
-                    self.attn_counter, *(self.zq.triple() if emit_q80 else ()))
+        getattr(self.k, addr.attn)(
+            self.qkv_out, self.qkv_ld, self.k_cache[l], self.v_cache[l],
+            self.zbuf[:B], *addr.where, B, c.n_heads0, self.kv_mul,
+            c.head_dim, self.attn_splits, self.attn_ml, self.attn_o,
+            *addr.attn_scratch, *(self.zq.triple() if emit_q80 else ()))
 
     def _swiglu_q80(self, out13, rows: int, qb: QuantBuf, *act):
         """act(w1 x) * (w3 x) over the fused W1|W3 output -> Q80 triple."""
@@ -648,8 +642,7 @@ class HipTransformer:
         """Run one step over tokens[:B] at positions pos..pos+B-1, writing
         logits into logits0 (and the gather buffer under TP). Everything
         stays on device — this function is graph-capturable."""
-        c, k = self.cfg, self.k
-        NB = _pow2_batch(B)
+        c = self.cfg
         tp_def_ok = (not self.tp_path
                      or (c.sync_type == Q80 and c.dim % 256 == 0))
         if (B == 1 and c.dim % 32 == 0 and tp_def_ok
@@ -659,18 +652,46 @@ class HipTransformer:
             return self._forward_dense_deferred()
         if B >= 8 and self.prefill_bf16:
             return self._forward_prefill_bf16(B)
+        self._forward_explicit(B, self.seq_addr)
+
+    def _forward_explicit(self, B: int, addr: KVAddr):
+        """The explicit-norm schedule (norm_quant in front of every matmul)
+        over B rows under any addressing. All K/V rows of a step are written
+        before its attention launches, so rows of one sequence (a prompt
+        chunk) see each other.
+
+        A row step (addr.row_table) differs from the single-sequence step
+        in five conditions below. Four follow from what a row step is:
+          - its tokens arrive in row_tokens, staged with the table in one
+            copy;
+          - the QKV GEMV with the rope epilogue reads `pos` and has no
+            row-table form, so the separate rope/KV launch always runs;
+          - its rows belong to different sequences that each sample from
+            their own logits row, so the logits are always computed, and
+            greedy feedback (an argmax into tokens[0], which a row step
+            does not read) never runs;
+          - under TP the vocab shards are concatenated inside the step,
+            where a captured row graph's per-row samplers read them; the
+            single-sequence caller (`forward`) does it after the step.
+        One is history only: a one-row step could take the fused FFN GEMV,
+        but DLLAMA_FUSED_FFN (measured slower) was never wired to row
+        steps, and the pinned launch traces keep it that way."""
+        c, k = self.cfg, self.k
+        NB = _pow2_batch(B)
+        rows = addr.row_table
         self.ssq.zero_()
-        k.embed_gather(self.embedding, self.tokens, self.x, NB, self.ssq[0])
+        k.embed_gather(self.embedding, self.row_tokens if rows else self.tokens,
+                       self.x, NB, self.ssq[0])
         slot = 0
         for l, lw in enumerate(self.layers):
             # attention block
-            if self.fused_rope and NB < 8:
+            if self.fused_rope and NB < 8 and not rows:
                 self._norm_quant(lw["norm0"], slot, NB)
                 self._gemv_rope(l, lw, NB)
             else:
                 self._norm_mm(lw["qkv"], lw["norm0"], slot, self.qkv_out, NB)
-                self._qknorm_rope_kv(l, lw, B)
-            self._attn(l, B)
+                self._qknorm_rope_kv(l, lw, B, addr)
+            self._attn(l, B, addr)
             self._proj_merge(lw["wo"], self.zq, slot + 1, NB)
             slot += 1
 
@@ -681,7 +702,8 @@ class HipTransformer:
                 self._moe_ffn(B, NB, lw, slot + 1)
             else:
                 gelu = c.hidden_act == HIDDEN_ACT_GELU
-                if NB == 1 and c.ff_dim0 % 32 == 0 and self.fused_ffn:
+                if (NB == 1 and c.ff_dim0 % 32 == 0 and self.fused_ffn
+                        and not rows):
                     # fused W1|W3 GEMV + SwiGLU + Q80 emit (one launch
                     # replacing gemv + swiglu_q80)
                     self._norm_quant(lw["norm1"], slot, NB)
@@ -694,9 +716,11 @@ class HipTransformer:
                 self._proj_merge(lw["w2"], self.dq, slot + 1, NB)
             slot += 1
 
-        if self.skip_logits and B > 1:
+        if self.skip_logits and B > 1 and not rows:
             return
-        self._logits(B, NB, slot)
+        self._logits(B, NB, slot, feedback=not rows)
+        if rows and self.tp_path:
+            k.logits_concat(self.logits_full, self.logits_gather[NB], B)
 
     def _forward_prefill_bf16(self, B: int):
         """Dense prompt chunks as hipBLASLt bf16 GEMMs over the weight
@@ -722,8 +746,8 @@ class HipTransformer:
         slot = 0
         for l, lw in enumerate(self.layers):
             self.qkv_out[:NB].copy_(norm_mm(lw["norm0"], slot, lw["qkv_bf16"]))
-            self._qknorm_rope_kv(l, lw, B)
-            self._attn(l, B, emit_q80=False)
+            self._qknorm_rope_kv(l, lw, B, self.seq_addr)
+            self._attn(l, B, self.seq_addr, emit_q80=False)
             partial = torch.mm(self.zbuf[:NB].bfloat16(),
                                lw["wo_bf16"].t()).float()
             k.add_ssq(x[:NB], partial, self.ssq[slot + 1], NB)
@@ -767,8 +791,8 @@ class HipTransformer:
             else:
                 k.q40_gemv(lw["qkv"].qs, lw["qkv"].scales, *self.xq.triple(),
                            self.qkv_out, 1, ssq_in=sin, eps=eps)
-                self._qknorm_rope_kv(l, lw, 1)
-            self._attn(l, 1)
+                self._qknorm_rope_kv(l, lw, 1, self.seq_addr)
+            self._attn(l, 1, self.seq_addr)
             # wo: residual fold + deferred Q80 emit of x*norm1 for the FFN
             self._proj_merge_deferred(lw["wo"], self.zq, slot + 1, lw["norm1"])
             slot += 1
@@ -858,38 +882,45 @@ class HipTransformer:
 
         When a decode graph is captured and B==1, this is a single hipGraph
         replay (the graph advances the device position itself)."""
-        self._rows_only()
         B = tokens.shape[0]
         assert B <= self.n_batches
-        p0 = int(positions[0])
-        if p0 + B > self.cfg.seq_len:
-            raise ValueError(
-                f"position {p0}+{B} exceeds seq_len {self.cfg.seq_len} "
-                "(rebuild with a larger --max-seq-len / seq_len)")
+        p0 = self._first_position(positions, B)
         self.tokens[:B].copy_(tokens.to(self.device), non_blocking=True)
         if B == 1 and self._graph is not None:
             self._replay_decode(p0)
-        elif B == self.n_batches and not self._pf_failed:
-            # full prefill chunks replay a captured graph (eager chunk cost
-            # is host-launch-bound: ~400 python kernel launches)
-            g = self._pf_graphs.get(self.skip_logits)
-            if g is None:
-                g = self._capture_prefill_graph(self.skip_logits)
-            self.pos.fill_(p0)
-            self._graph_pos = None
-            if g is not None:
-                g.replay()
-            else:
-                self.forward_buffers(B)
         else:
-            self.pos.fill_(p0)
-            self._graph_pos = None
-            self.forward_buffers(B)
+            g = None
+            if B == self.n_batches and not self._pf_failed:
+                # full prefill chunks replay a captured graph (eager chunk
+                # cost is host-launch-bound: ~400 python kernel launches)
+                g = (self._pf_graphs.get(self.skip_logits)
+                     or self._capture_prefill_graph(self.skip_logits))
+            self._step_at(B, p0, g)
         if self.tp_path:
             NBp = _pow2_batch(B)
             self.k.logits_concat(self.logits_full, self.logits_gather[NBp], B)
             return self.logits_full[:B]
         return self.logits0[:B]
+
+    def _first_position(self, positions, B: int) -> int:
+        """positions[0] of a single-sequence step of B rows, checked."""
+        self._rows_only()
+        p0 = int(positions[0])
+        if p0 + B > self.cfg.seq_len:
+            raise ValueError(
+                f"position {p0}+{B} exceeds seq_len {self.cfg.seq_len} "
+                "(rebuild with a larger --max-seq-len / seq_len)")
+        return p0
+
+    def _step_at(self, B: int, p0: int, graph=None):
+        """One step of B rows at p0 outside the decode graph: eager
+        launches, or a replay of a graph that was captured from them."""
+        self.pos.fill_(p0)
+        self._graph_pos = None  # the decode graph no longer owns the position
+        if graph is not None:
+            graph.replay()
+        else:
+            self.forward_buffers(B)
 
     def _replay_decode(self, p0: int):
         """One replay of the captured decode graph on tokens[0] at p0."""
@@ -937,13 +968,8 @@ class HipTransformer:
         launches). Only the token id and the parameters go to the device and
         {token, status} comes back; the logits stay in place (last_logits),
         so a None result can be resampled by the caller."""
-        self._rows_only()
         assert tokens.shape[0] == 1
-        p0 = int(positions[0])
-        if p0 + 1 > self.cfg.seq_len:
-            raise ValueError(
-                f"position {p0}+1 exceeds seq_len {self.cfg.seq_len} "
-                "(rebuild with a larger --max-seq-len / seq_len)")
+        p0 = self._first_position(positions, 1)
         smp, NB = self._sampler(), self.n_batches
         self._step_host[0] = int(tokens[0])
         smp.fill_params(self._step_host[NB:].view(torch.float64), coin,
@@ -956,9 +982,7 @@ class HipTransformer:
             if not self._graph_samples:
                 smp.launch(self.last_logits())
         else:
-            self.pos.fill_(p0)
-            self._graph_pos = None
-            self.forward_buffers(1)
+            self._step_at(1, p0)
             smp.launch(self.last_logits())
         return smp.read()
 
@@ -1012,6 +1036,11 @@ class HipTransformer:
             self.row_tokens = io[:NB]
             self.row_params = io[NB:5 * NB].view(torch.float64).view(NB, 4)
             self.rows = io[5 * NB:].view(torch.int32).view(NB, 2)
+            if self.page_map is not None:
+                self.row_addr = KVAddr("_paged", self.rows, self.page_table,
+                                       self.page_size)
+            else:
+                self.row_addr = KVAddr("_rows", self.rows)
             self.rows_sample_out = torch.zeros(NB, 2, dtype=torch.int64,
                                                device=dev)  # token, status
             self._rows_host = torch.zeros(6 * NB, dtype=torch.int64)
@@ -1075,34 +1104,9 @@ class HipTransformer:
         return B, table, is_decode_step(slots)
 
     def _forward_rows_buffers(self, B: int):
-        """One ragged step over row_tokens[:B] addressed by the row table:
-        forward_buffers' explicit-norm schedule with the unfused QKV matmul,
-        rope/KV write and attention per table row. All K/V rows are written
-        before the attention launch, so rows of one sequence (a prompt
-        chunk) see each other. Everything stays on device: capturable."""
-        c, k = self.cfg, self.k
-        NB = _pow2_batch(B)
-        self.ssq.zero_()
-        k.embed_gather(self.embedding, self.row_tokens, self.x, NB, self.ssq[0])
-        slot = 0
-        for l, lw in enumerate(self.layers):
-            self._norm_mm(lw["qkv"], lw["norm0"], slot, self.qkv_out, NB)
-            self._rope_kv_rows(l, lw, B)
-            self._attn_rows(l, B)
-            self._proj_merge(lw["wo"], self.zq, slot + 1, NB)
-            slot += 1
-            if c.is_moe:
-                self._norm_quant(lw["norm1"], slot, NB, self.t_norm[:NB])
-                self._moe_ffn(B, NB, lw, slot + 1)
-            else:
-                self._norm_mm(lw["w13"], lw["norm1"], slot, self.ff_out, NB)
-                self._swiglu_q80(self.ff_out, NB, self.dq,
-                                 c.hidden_act == HIDDEN_ACT_GELU)
-                self._proj_merge(lw["w2"], self.dq, slot + 1, NB)
-            slot += 1
-        self._logits(B, NB, slot, feedback=False)
-        if self.tp_path:
-            k.logits_concat(self.logits_full, self.logits_gather[NB], B)
+        """One ragged step over row_tokens[:B] addressed by the row table.
+        Everything stays on device: capturable."""
+        self._forward_explicit(B, self.row_addr)
 
     def _rows_step_and_sample(self, B: int):
         self._forward_rows_buffers(B)
@@ -1117,18 +1121,8 @@ class HipTransformer:
         try:
             for b in range(B):
                 self._row_sampler(b)  # buffers exist before the capture
-            torch.cuda.synchronize(self.device)
-            s = torch.cuda.Stream(self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(s):
-                for _ in range(2):
-                    self._rows_step_and_sample(B)
-            torch.cuda.current_stream(self.device).wait_stream(s)
-            torch.cuda.synchronize(self.device)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._rows_step_and_sample(B)
-                self.k.rows_advance(self.rows, B)
+            g = self._capture(lambda: self._rows_step_and_sample(B), warmups=2,
+                              tail=lambda: self.k.rows_advance(self.rows, B))
             self._row_graphs[B] = g
             return g
         except Exception as e:  # noqa: BLE001
@@ -1216,38 +1210,34 @@ class HipTransformer:
         self._pf_graphs.clear()  # prefill graphs also reference the scratch
         self._row_graphs.clear()  # and so do the row-step graphs
 
-    def _warm_and_capture(self, B: int, warmups: int, advance_pos: bool = False,
-                          sample: bool = False):
-        """Run forward_buffers(B) `warmups` times on a side stream
-        (allocations, lazy kernel loads), then capture it as a hipGraph;
-        sample appends the sampler launches over the step's logits row,
-        advance_pos the device position increment."""
-        if sample:
-            self._sampler()  # its buffers exist before anything is captured
-        torch.cuda.synchronize(self.device)
-        s = torch.cuda.Stream(self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
+    def _capture(self, body, warmups: int, tail=None):
+        """The capture procedure: synchronise, run body() `warmups` times on
+        a side stream (allocations, lazy kernel loads), join and
+        synchronise, then capture body() and tail() as a hipGraph. The tail
+        (a position advance) is captured but never run while warming up.
+        Buffers that body() would create exist before this is called."""
+        dev = self.device
+        torch.cuda.synchronize(dev)
+        s = torch.cuda.Stream(dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(s):
             for _ in range(warmups):
-                self.forward_buffers(B)
-                if sample:
-                    self._sampler().launch(self.last_logits())
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        torch.cuda.synchronize(self.device)
+                body()
+        torch.cuda.current_stream(dev).wait_stream(s)
+        torch.cuda.synchronize(dev)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self.forward_buffers(B)
-            if sample:
-                self._sampler().launch(self.last_logits())
-            if advance_pos:
-                self.k.pos_inc(self.pos, 1)
+            body()
+            if tail is not None:
+                tail()
         return g
 
     def _capture_prefill_graph(self, skip_logits: bool):
         try:
             saved = self.skip_logits
             self.skip_logits = skip_logits
-            g = self._warm_and_capture(self.n_batches, warmups=1)
+            g = self._capture(lambda: self.forward_buffers(self.n_batches),
+                              warmups=1)
             self.skip_logits = saved
             self._pf_graphs[skip_logits] = g
             return g
@@ -1265,7 +1255,15 @@ class HipTransformer:
         sampler runs inside it, between the step and the pos advance."""
         self._rows_only()
         sample = bool(self.device_sampling)
-        self._graph = self._warm_and_capture(1, warmups=2, advance_pos=True,
-                                             sample=sample)
+        if sample:
+            self._sampler()  # its buffers exist before anything is captured
+
+        def step():
+            self.forward_buffers(1)
+            if sample:
+                self._sampler().launch(self.last_logits())
+
+        self._graph = self._capture(
+            step, warmups=2, tail=lambda: self.k.pos_inc(self.pos, 1))
         self._graph_samples = sample
         self._graph_pos = None  # device pos unknown until first fill

@@ -1,13 +1,22 @@
 #!/usr/bin/env python3
-"""Launch-trace pin for `HipTransformer.forward_buffers`.
+"""Launch-trace pin for `HipTransformer`'s schedules.
 
 Which kernels run, in what order and on which buffers is decided in Python
 (`dllama_amd/models/hip_model.py`). This tool replays a matrix of model
 configurations on the CPU with a recorder in place of the HIP extension
 (`model.k`) and of the communicator (`model.comm`), and compares the
-resulting `(kernel, args)` lists with `tests/golden/launch_trace.json`. No
-GPU and no extension build are needed: the kernels never run, only the
-launch sequence is observed.
+resulting `(kernel, args)` lists with two goldens. No GPU and no extension
+build are needed: the kernels never run, only the launch sequence is
+observed.
+
+  tests/golden/launch_trace.json       the single-sequence step,
+      `forward_buffers(B)`, over BATCHES x MODES;
+  tests/golden/launch_trace_rows.json  row steps, `forward_rows`, over
+      ADDRESSINGS (row table; row table + page table) x ROW_STEPS x
+      ROW_MODES. A row step ignores `greedy_feedback` and `skip_logits`,
+      and the modes pin that it does. The per-row sampler launches of
+      `forward_rows_sample` are not traced: they are the same step followed
+      by one sampler launch per row, which the GPU tests cover.
 
 An argument is recorded in a canonical form that names no attribute:
 scalars as they are (keyword names included), tensors as `(dtype, shape,
@@ -18,12 +27,12 @@ appearance in the trace (zero-initialised activation and scratch buffers,
 temporaries). Renaming a buffer leaves a trace unchanged; another weight,
 `ssq` slot, slice or argument order does not.
 
-The golden also holds a digest of every weight that
+The first golden also holds a digest of every weight that
 `HipTransformer.synthetic(cfg, device="cpu", seed=1234)` draws, keyed by
 role and layer, so the RNG draw order stays comparable across commits.
 
-  python tools/launch_trace.py            check against the golden
-  python tools/launch_trace.py --record   write the golden
+  python tools/launch_trace.py            check against both goldens
+  python tools/launch_trace.py --record   write both goldens
 """
 
 import contextlib
@@ -46,6 +55,7 @@ from dllama_amd.parallel.comm import SingleComm  # noqa: E402
 from dllama_amd.quants import F32, Q80  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "launch_trace.json")
+GOLDEN_ROWS = os.path.join(ROOT, "tests", "golden", "launch_trace_rows.json")
 
 # ------------------------------------------------------------------ matrix
 
@@ -83,6 +93,26 @@ ENVS = {
 }
 BATCHES = [1, 3, 8, 20, 32]
 MODES = [(False, False), (True, False), (False, True)]  # (greedy, skip_logits)
+
+# row steps. name -> (constructor arguments, {slot: pool pages}); no page is
+# shared and every position of ROW_STEPS is mapped
+ADDRESSINGS = {
+    "table": (dict(n_slots=3), {}),
+    "paged": (dict(n_slots=3, kv_pages=12, page_size=8),
+              {0: [0, 1, 2], 1: [3, 4], 2: [5, 6, 7, 8]}),
+}
+# name -> (tokens, slots, positions)
+ROW_STEPS = {
+    # NB=1, a slot other than 0
+    "one_decode_row": ([5], [1], [0]),
+    # NB=4: the GEMV side of _mm
+    "all_decode": ([7, 11, 13], [0, 1, 2], [3, 9, 20]),
+    # two prompt chunks and one decode row, NB=16: the GEMM side of _mm
+    "mixed": ([17, 19, 23, 29, 31, 37, 41, 43, 47],
+              [0, 0, 0, 0, 0, 1, 2, 2, 2],
+              [4, 5, 6, 7, 8, 10, 21, 22, 23]),
+}
+ROW_MODES = [(True, False), (False, True)]  # both ignored by a row step
 
 
 def applies(arch: str, env: str) -> bool:
@@ -248,9 +278,8 @@ def write_models(workdir: str) -> dict:
     return paths
 
 
-def trace_config(path: str, arch: str, sync: str, env: str) -> list:
-    """The traces of one model over BATCHES x MODES, each as a list of
-    `(lines, calls)`."""
+def _recorded_model(path: str, arch: str, sync: str, env: str, **ctor):
+    """(model, its recording kernels, its content keys)."""
     force_sync, sync_type = SYNCS[sync]
     m = mf.ModelFile(path, sync_type=sync_type)
     cfg = ModelConfig.from_header(m.header)
@@ -261,15 +290,39 @@ def trace_config(path: str, arch: str, sync: str, env: str) -> list:
             mock.patch.object(hm, "hip_ops", lambda: kernels):
         model = hm.HipTransformer.from_file(
             m, cfg, device="cpu", comm=RecordingComm(kernels),
-            force_sync=force_sync)
+            force_sync=force_sync, **ctor)
     assert model.k is kernels and model.comm.kernels is kernels
-    content = content_keys(model)
+    return model, kernels, content_keys(model)
+
+
+def trace_config(path: str, arch: str, sync: str, env: str) -> list:
+    """The traces of one model over BATCHES x MODES, each as a list of
+    `(lines, calls)`."""
+    model, kernels, content = _recorded_model(path, arch, sync, env)
     out = []
     for B in BATCHES:
         for greedy, skip in MODES:
             model.greedy_feedback, model.skip_logits = greedy, skip
             kernels.trace = Trace(content)
             model.forward_buffers(B)
+            out.append((kernels.trace.lines(), kernels.trace.calls))
+    return out
+
+
+def trace_rows_config(path: str, arch: str, sync: str, env: str,
+                      addressing: str) -> list:
+    """The traces of one model over ROW_STEPS x ROW_MODES, through the
+    public row API only."""
+    ctor, pages = ADDRESSINGS[addressing]
+    model, kernels, content = _recorded_model(path, arch, sync, env, **ctor)
+    for slot, ids in pages.items():
+        model.set_slot_pages(slot, ids)
+    out = []
+    for tokens, slots, positions in ROW_STEPS.values():
+        for greedy, skip in ROW_MODES:
+            model.greedy_feedback, model.skip_logits = greedy, skip
+            kernels.trace = Trace(content)
+            model.forward_rows(tokens, slots, positions)
             out.append((kernels.trace.lines(), kernels.trace.calls))
     return out
 
@@ -302,16 +355,63 @@ def synthetic_weights() -> dict:
 
 # ------------------------------------------------------------ golden file
 
-def build_live():
+class Pin:
+    """One golden file: its header (the axes of a model's runs), the models
+    it covers, how a model is traced and how a run is labelled."""
+
+    def __init__(self, path, header, models, trace, labels, weights=False):
+        self.path = path
+        self.header = json.loads(json.dumps(header))  # as the file holds it
+        self.models = models    # () -> (name, arguments of trace after path)
+        self.trace = trace
+        self.labels = labels    # header -> one label per run of a model
+        self.weights = weights  # also pins synthetic()'s draws
+
+
+def _forward_models():
+    for arch, sync, env in configs():
+        yield f"{arch}/{sync}/{env}", (arch, sync, env)
+
+
+def _rows_models():
+    for arch, sync, env in configs():
+        for addressing in ADDRESSINGS:
+            yield (f"{arch}/{sync}/{env}/{addressing}",
+                   (arch, sync, env, addressing))
+
+
+def _mode_labels(head: str, modes) -> list:
+    return [f"{head} greedy_feedback={g} skip_logits={s}" for g, s in modes]
+
+
+FORWARD = Pin(
+    GOLDEN, {"batches": BATCHES, "modes": MODES}, _forward_models,
+    trace_config,
+    lambda h: [s for B in h["batches"]
+               for s in _mode_labels(f"B={B}", h["modes"])],
+    weights=True)
+ROWS = Pin(
+    GOLDEN_ROWS,
+    {"addressings": {a: {"constructor": ctor,
+                         "pages": {str(s): p for s, p in pages.items()}}
+                     for a, (ctor, pages) in ADDRESSINGS.items()},
+     "steps": ROW_STEPS, "modes": ROW_MODES},
+    _rows_models, trace_rows_config,
+    lambda h: [s for step in h["steps"]
+               for s in _mode_labels(f"step={step}", h["modes"])])
+PINS = (FORWARD, ROWS)
+_BODY = ("calls", "traces", "configs", "synthetic_weights")
+
+
+def build_live(pin: Pin = FORWARD):
     """(golden-shaped dict, {config: [calls per trace]}) of this tree."""
     call_ids, traces, trace_ids = {}, [], {}
     cfgs, live_calls = {}, {}
     with _single_thread(), tempfile.TemporaryDirectory() as workdir:
         paths = write_models(workdir)
-        for arch, sync, env in configs():
-            name = f"{arch}/{sync}/{env}"
+        for name, args in pin.models():
             ids = []
-            results = trace_config(paths[arch], arch, sync, env)
+            results = pin.trace(paths[args[0]], *args)
             for lines, _ in results:
                 t = tuple(call_ids.setdefault(s, len(call_ids)) for s in lines)
                 if t not in trace_ids:
@@ -320,51 +420,49 @@ def build_live():
                 ids.append(trace_ids[t])
             cfgs[name] = ids
             live_calls[name] = [calls for _, calls in results]
-        weights = synthetic_weights()
-    gold = {
-        "batches": BATCHES,
-        "modes": [list(m) for m in MODES],
-        # "kernel:digest" of every distinct call; a trace lists indices into
-        # it, a config lists one trace index per (batch, mode), batch-major
-        "calls": list(call_ids),
-        "traces": traces,
-        "configs": cfgs,
-        "synthetic_weights": weights,
-    }
+        weights = synthetic_weights() if pin.weights else None
+    gold = dict(pin.header)
+    # "kernel:digest" of every distinct call; a trace lists indices into
+    # it, a config lists one trace index per run, first header axis major
+    gold.update(calls=list(call_ids), traces=traces, configs=cfgs)
+    if pin.weights:
+        gold["synthetic_weights"] = weights
     return gold, live_calls
 
 
-def compare(gold: dict, live: dict, live_calls: dict) -> list:
+def compare(gold: dict, live: dict, live_calls: dict,
+            pin: Pin = FORWARD) -> list:
     """Human-readable mismatches (empty when the pin holds)."""
     errs = []
-    for key in ("batches", "modes"):
-        if gold[key] != live[key]:
-            errs.append(f"{key}: golden {gold[key]} != live {live[key]}")
+    for key in pin.header:
+        if gold.get(key) != live[key]:
+            errs.append(f"{key}: golden {gold.get(key)} != live {live[key]}")
     if sorted(gold["configs"]) != sorted(live["configs"]):
         errs.append("configuration matrix differs from the golden: "
                     f"{sorted(set(gold['configs']) ^ set(live['configs']))}")
     if errs:
         return errs
-    n_modes = len(gold["modes"])
+    labels = pin.labels(gold)
     for name, want_ids in gold["configs"].items():
+        if len(want_ids) != len(live["configs"][name]):
+            errs.append(f"{name}: golden {len(want_ids)} runs != live "
+                        f"{len(live['configs'][name])}")
         for i, (wi, gi) in enumerate(zip(want_ids, live["configs"][name])):
             want = [gold["calls"][c] for c in gold["traces"][wi]]
             got = [live["calls"][c] for c in live["traces"][gi]]
             if want == got:
                 continue
-            B = gold["batches"][i // n_modes]
-            greedy, skip = gold["modes"][i % n_modes]
             at = next((j for j, (a, b) in enumerate(zip(want, got)) if a != b),
                       min(len(want), len(got)))
             calls = live_calls[name][i]
             errs.append(
-                f"{name} B={B} greedy_feedback={greedy} skip_logits={skip}: "
+                f"{name} {labels[i]}: "
                 f"first difference at call {at} "
                 f"(golden {len(want)} calls, live {len(got)})\n"
                 f"  golden: {want[at] if at < len(want) else '<end>'}\n"
                 f"  live:   {got[at] if at < len(got) else '<end>'}\n"
                 f"  live call: {calls[at] if at < len(calls) else '<end>'}")
-    for arch, want in gold["synthetic_weights"].items():
+    for arch, want in gold.get("synthetic_weights", {}).items():
         got = live["synthetic_weights"].get(arch, {})
         for role in sorted(set(want) | set(got)):
             if want.get(role) != got.get(role):
@@ -378,36 +476,40 @@ def dump(gold: dict) -> str:
     def block(items, open_, close):
         return open_ + "\n" + ",\n".join(items) + "\n" + close
     js = lambda v: json.dumps(v, separators=(",", ":"))  # noqa: E731
-    parts = [
-        f'"batches":{js(gold["batches"])}',
-        f'"modes":{js(gold["modes"])}',
+    parts = [f'"{k}":{js(v)}' for k, v in gold.items() if k not in _BODY]
+    parts += [
         '"calls":' + block([js(c) for c in gold["calls"]], "[", "]"),
         '"traces":' + block([js(t) for t in gold["traces"]], "[", "]"),
         '"configs":' + block([f"{js(k)}:{js(v)}"
                               for k, v in gold["configs"].items()], "{", "}"),
-        '"synthetic_weights":' + json.dumps(gold["synthetic_weights"], indent=1),
     ]
+    if "synthetic_weights" in gold:
+        parts.append('"synthetic_weights":'
+                     + json.dumps(gold["synthetic_weights"], indent=1))
     return "{\n" + ",\n".join(parts) + "\n}\n"
 
 
 def main(argv):
-    live, live_calls = build_live()
-    if "--record" in argv:
-        with open(GOLDEN, "w") as f:
-            f.write(dump(live))
-        print(f"recorded {len(live['configs'])} models x "
-              f"{len(BATCHES) * len(MODES)} runs, {len(live['traces'])} "
-              f"distinct traces, {len(live['calls'])} distinct calls")
-        return 0
-    with open(GOLDEN) as f:
-        gold = json.load(f)
-    errs = compare(gold, live, live_calls)
-    for e in errs[:10]:
-        print(e)
-    print(f"{len(errs)} mismatches" if errs else
-          f"launch traces match the golden ({len(live['configs'])} models x "
-          f"{len(BATCHES) * len(MODES)} runs)")
-    return 1 if errs else 0
+    status = 0
+    for pin in PINS:
+        live, live_calls = build_live(pin)
+        what = (f"{os.path.basename(pin.path)}: {len(live['configs'])} "
+                f"models x {len(pin.labels(pin.header))} runs")
+        if "--record" in argv:
+            with open(pin.path, "w") as f:
+                f.write(dump(live))
+            print(f"recorded {what}, {len(live['traces'])} distinct traces, "
+                  f"{len(live['calls'])} distinct calls")
+            continue
+        with open(pin.path) as f:
+            gold = json.load(f)
+        errs = compare(gold, live, live_calls, pin)
+        for e in errs[:10]:
+            print(e)
+        print(f"{what}: {len(errs)} mismatches" if errs else
+              f"launch traces match the golden ({what})")
+        status |= bool(errs)
+    return status
 
 
 if __name__ == "__main__":
