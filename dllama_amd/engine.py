@@ -229,6 +229,11 @@ class BatchEngine:
                                  share=share_prefixes)
             for slot in range(model.n_slots):
                 model.clear_slot(slot)
+        # short-context row steps take the wide single-launch attention that
+        # the single-sequence decode takes, so a sequence generates the same
+        # alone and batched
+        if hasattr(model, "set_wide_rows"):
+            model.set_wide_rows()
         self.tokenizer = tokenizer
         self.n_batches = min(n_batches, getattr(model, "n_batches", n_batches))
         self.seq_len = model.cfg.seq_len

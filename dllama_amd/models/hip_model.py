@@ -218,15 +218,25 @@ class HipTransformer:
         # fused quantize-into-wire sync: validated bit-identical on hardware
         # (test_sync_quant_pack_matches_two_kernel_path); default on
         self.fused_sync = flag("DLLAMA_FUSED_SYNC", "1")
-        # adaptive K-split schedule: S=1 fused single-kernel attention below
-        # pos 256 (no combine launch), S=8 to the threshold, S=16 beyond
-        # (tools/attn_kv16_probe: S=16 wins from ~pos 512). The decode graph
-        # is recaptured when pos crosses a boundary. DLLAMA_ADAPTIVE_SPLITS=0
-        # (or an explicit DLLAMA_ATTN_SPLITS) pins S.
+        # adaptive K-split schedule: S=1 (the wide single-launch attention,
+        # no combine launch) below wide_thresh, S=8 to the threshold, S=16
+        # beyond (tools/attn_kv16_probe: S=16 wins from ~pos 512). The decode
+        # graph is recaptured when pos crosses a boundary.
+        # DLLAMA_ADAPTIVE_SPLITS=0 (or an explicit DLLAMA_ATTN_SPLITS) pins S.
         self.adaptive_thresh = int(env.get("DLLAMA_ADAPTIVE_SPLITS", "512"))
         if ("DLLAMA_ATTN_SPLITS" in env
                 and "DLLAMA_ADAPTIVE_SPLITS" not in env):
             self.adaptive_thresh = 0
+        # positions below this take the wide kernel: the measured crossover
+        # against the best split + combine pair, rounded down to a multiple
+        # of the kernel's 256-timestep round (profiles/r07_wide_attention.md).
+        # DLLAMA_ATTN_WIDE=<pos> moves it, 0 turns the tier off.
+        self.wide_thresh = int(env.get("DLLAMA_ATTN_WIDE", "256"))
+        # row steps (forward_rows) take the tier on request: set_wide_rows,
+        # which BatchEngine calls, or DLLAMA_ATTN_WIDE_ROWS=1
+        self.wide_rows = flag("DLLAMA_ATTN_WIDE_ROWS", "0")
+        # the S in force above the wide tier, put back when a step leaves it
+        self._splits_above = self.attn_splits if self.attn_splits != 1 else 8
         # measured-slower fusions kept for shape experiments (profiles r02):
         # the 16-wave fused FFN streams worse than the 4-wave GEMV + swiglu
         # pair, and per-wave gate recompute adds ~8 us to each MoE consumer
@@ -889,6 +899,8 @@ class HipTransformer:
         if B == 1 and self._graph is not None:
             self._replay_decode(p0)
         else:
+            self._follow_wide_tier(
+                p0 + B - 1, emit_q80=not (B >= 8 and self.prefill_bf16))
             g = None
             if B == self.n_batches and not self._pf_failed:
                 # full prefill chunks replay a captured graph (eager chunk
@@ -921,6 +933,18 @@ class HipTransformer:
             graph.replay()
         else:
             self.forward_buffers(B)
+
+    def _follow_wide_tier(self, last_pos: int, emit_q80: bool):
+        """S of a step outside the decode graph (a prompt chunk, an eager
+        decode step) whose last row is at last_pos: S=1 while the wide tier
+        holds there, so that a sequence computes the same alone, as rows and
+        with or without the graph; above the tier the S that was set before
+        it, as such steps always ran. Looked at on every step, so S=1 never
+        outlives the tier; a step without Q80 output has no wide kernel and
+        stays out of it."""
+        wide = emit_q80 and self._pick_splits(last_pos) == 1
+        if wide != (self.attn_splits == 1):
+            self._set_attn_splits(1 if wide else self._splits_above)
 
     def _replay_decode(self, p0: int):
         """One replay of the captured decode graph on tokens[0] at p0."""
@@ -982,6 +1006,7 @@ class HipTransformer:
             if not self._graph_samples:
                 smp.launch(self.last_logits())
         else:
+            self._follow_wide_tier(p0, emit_q80=True)
             self._step_at(1, p0)
             smp.launch(self.last_logits())
         return smp.read()
@@ -1136,7 +1161,7 @@ class HipTransformer:
     def _run_rows(self, B: int, table, decode_only: bool, sample: bool):
         """The staged step: a replay of the B-row graph when every row is a
         decode row, else eager launches."""
-        sp = self._pick_splits(max(p for _, p in table))
+        sp = self._pick_splits(max(p for _, p in table), rows=True)
         if sp != self.attn_splits:
             self._set_attn_splits(sp)  # drops the row graphs with the scratch
         g = None
@@ -1183,16 +1208,32 @@ class HipTransformer:
 
     # ------------------------------------------------------------ graphs
 
-    def _pick_splits(self, pos: int) -> int:
-        # S=8 short context, S=16 past the threshold (tools/attn_kv16_probe).
-        # Two measured-slower variants exist behind env flags and are never
-        # auto-picked: the S=1 fused single kernel (13.5 us vs the ~11 us
-        # pair) and the GQA-grouped split (DLLAMA_GQA_ATTN).
+    def _pick_splits(self, pos: int, rows: bool = False) -> int:
+        # S=1 below wide_thresh: with Q80 output that is the wide
+        # single-launch kernel, one memory latency and an LDS merge instead
+        # of split + combine. S=8 from there, S=16 past the threshold
+        # (tools/attn_kv16_probe). The GQA-grouped split (DLLAMA_GQA_ATTN)
+        # measured slower and is never auto-picked.
+        # rows: a row step. The model's own default keeps its pinned launch
+        # list (tests/golden/launch_trace_rows.json: S=8 at short positions)
+        # and skips the wide tier; S=1 is never handed to the pair there.
+        # set_wide_rows turns the tier on for row steps: BatchEngine calls
+        # it.
         if not self.adaptive_thresh:
             return self.attn_splits
+        if ((self.wide_rows or not rows)
+                and pos < min(self.wide_thresh, self.adaptive_thresh)):
+            return 1
         if pos < self.adaptive_thresh:
             return 8
         return 16 if pos < 2048 else 32  # S=32 at 4k ctx: +12.5% same-box
+
+    def set_wide_rows(self, on: bool = True):
+        """Let row steps take the wide tier as single-sequence steps do. A
+        caller that serves sequences through forward_rows (BatchEngine) asks
+        for it, so that a sequence generates the same alone and batched; the
+        model's own default stays the pinned S=8 launch list."""
+        self.wide_rows = on
 
     def _set_attn_splits(self, s: int):
         """Switch the flash-decode K-split count mid-stream (long-context
@@ -1201,6 +1242,8 @@ class HipTransformer:
         capture warmup's KV write at the current pos is overwritten by the
         next real step."""
         self.attn_splits = s
+        if s != 1:
+            self._splits_above = s
         self._alloc_attn_scratch()
         if self._graph is not None:
             pos_saved = int(self.pos.item())

@@ -55,20 +55,14 @@ struct PagedRows {
 // Stage 1: grid (H0, B, S); split sp covers t = (sp*4+wave) + 4*S*i — the
 // t-range is spread over S*4 waves so long contexts fill the chip.
 // Per-split (m, l, o) goes to scratch; stage 2 combines the S partials.
-template <int VEC, typename KVT, bool FUSE = false, typename ROWS = SeqRows>
+template <int VEC, typename KVT, typename ROWS = SeqRows>
 __global__ void k_attn_split(const float *__restrict__ q, int q_ld,
                              const KVT *__restrict__ kc_all,
                              const KVT *__restrict__ vc_all,
                              const ROWS rows,
                              int n_heads0, int kv_mul, int kv_dim0, float scale,
                              float *__restrict__ ml_scratch,
-                             float *__restrict__ o_scratch,
-                             int *__restrict__ counter,
-                             float *__restrict__ y,
-                             int8_t *__restrict__ zq,
-                             float *__restrict__ zs,
-                             float *__restrict__ zbs) {
-    (void)counter; (void)y; (void)zq; (void)zs; (void)zbs;
+                             float *__restrict__ o_scratch) {
     const int h0 = blockIdx.x;
     const int b = blockIdx.y;
     const int sp = blockIdx.z;
@@ -206,58 +200,230 @@ __global__ void k_attn_split(const float *__restrict__ q, int q_ld,
     if (wave == 0) {
         const float L = sl[0] * __expf(sm[0] - M) + sl[1] * __expf(sm[1] - M)
                       + sl[2] * __expf(sm[2] - M) + sl[3] * __expf(sm[3] - M);
-        if constexpr (FUSE) {
-            // S==1 single-kernel path (short contexts): normalize and emit
-            // the Q80 triple of this head directly — no scratch round-trip,
-            // no combine launch (the 2-kernel pair costs ~11 us in-graph at
-            // pos<256 where the actual KV read is microseconds)
-            const float invL = 1.0f / L;
-            float vv[VEC];
+        if (lane == 0) {
+            ml_scratch[slot * 2] = M;
+            ml_scratch[slot * 2 + 1] = L;
+        }
+        #pragma unroll
+        for (int v = 0; v < VEC; v++) {
+            const int i = lane * VEC + v;
+            o_scratch[slot * hd + i] = so[0][i] + so[1][i] + so[2][i] + so[3][i];
+        }
+    }
+}
+
+// ------------------------------------------------- wide single-launch decode
+// S == 1 with Q80 output, for short contexts: grid (H0, B), one workgroup of
+// 16 waves per head, no scratch round trip and no combine launch. A round
+// covers 256 consecutive timesteps, t = round*256 + wave*16 + u*4 + group, so
+// a decode step below position 256 is ONE round: q, the four K chunks and
+// the 16 V rows of a lane are all loaded before the first reduction (the V
+// addresses do not depend on the softmax), and the kernel costs about one
+// memory latency plus the LDS merge. The 4-wave kernel it replaces covered
+// 64 timesteps per round with the V loads behind each round's softmax: about
+// nine dependent latencies at position 250, which is what made it slower
+// than the split + combine pair. Correct at any plen (further rounds run the
+// online softmax per wave); only its speed is tied to short contexts.
+
+// a lane's run of N consecutive cache elements, loaded as one vector
+template <typename T, int N>
+struct alignas(sizeof(T) * N) KVPack { T e[N]; };
+
+// A load of a 2-, 4- or 8-byte pack that the compiler keeps where it is
+// written. Plain loads of read-only memory are sunk towards their first use,
+// which puts the V loads behind the waits of the K dots; a relaxed atomic
+// load of wavefront scope is the same instruction with no cache-policy bits
+// and no wait of its own, but it keeps its place among the side effects.
+template <int BYTES> struct UIntOfSize;
+template <> struct UIntOfSize<2> { using type = unsigned short; };
+template <> struct UIntOfSize<4> { using type = unsigned int; };
+template <> struct UIntOfSize<8> { using type = unsigned long long; };
+template <typename P>
+__device__ __forceinline__ P load_in_order(const P *p) {
+    using U = typename UIntOfSize<sizeof(P)>::type;
+    const U u = __hip_atomic_load(reinterpret_cast<const U *>(p),
+                                  __ATOMIC_RELAXED,
+                                  __HIP_MEMORY_SCOPE_WAVEFRONT);
+    P r;
+    __builtin_memcpy(&r, &u, sizeof(P));
+    return r;
+}
+
+// the 16 (chunk u, row g) pairs of a wave's round: the V rows live in 16
+// named registers, not an indexed array the allocator could send to scratch
+#define ATTN_WIDE_ROWS(X) \
+    X(0, 0) X(0, 1) X(0, 2) X(0, 3) X(1, 0) X(1, 1) X(1, 2) X(1, 3) \
+    X(2, 0) X(2, 1) X(2, 2) X(2, 3) X(3, 0) X(3, 1) X(3, 2) X(3, 3)
+
+template <int VEC, typename KVT, typename ROWS>
+__global__ void __launch_bounds__(1024)
+k_attn_wide(const float *__restrict__ q, int q_ld,
+            const KVT *__restrict__ kc_all,
+            const KVT *__restrict__ vc_all,
+            const ROWS rows,
+            int n_heads0, int kv_mul, int kv_dim0, float scale,
+            int8_t *__restrict__ zq,
+            float *__restrict__ zs,
+            float *__restrict__ zbs) {
+    constexpr int NW = 16;         // waves per workgroup
+    constexpr int hd = VEC * WAVE;
+    constexpr int VEC16 = VEC * 4;  // q/k elems per lane within a 16-lane group
+    using KPack = KVPack<KVT, VEC16>;
+    using VPack = KVPack<KVT, VEC>;
+    const int h0 = blockIdx.x;
+    const int b = blockIdx.y;
+    // every row of a row table has its own length
+    const int plen = rows.position(b) + 1;
+    const KVT *kc = kc_all + rows.cache_base(b) * kv_dim0;
+    const KVT *vc = vc_all + rows.cache_base(b) * kv_dim0;
+    // provably wave-uniform: the round loop branches on it and every row
+    // address below is a wave-uniform base plus a lane offset
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+    const int lane = threadIdx.x % WAVE;
+    const int kv_off = (h0 / kv_mul) * hd;
+    const int lane16 = lane & 15;
+    const int group = lane >> 4;
+
+    // q first; it is scaled on the score so that nothing uses it (and waits
+    // for it) before the K and V loads have issued
+    float qreg[VEC16];
+    #pragma unroll
+    for (int v = 0; v < VEC16; v++)
+        qreg[v] = q[(int64_t)b * q_ld + h0 * hd + lane16 * VEC16 + v];
+
+    float m = -1e30f, l = 0.0f, o[VEC];
+    #pragma unroll
+    for (int v = 0; v < VEC; v++) o[v] = 0.0f;
+
+    // A 4-timestep chunk starts at a multiple of 4, so it lies in one page
+    // for every page size >= 4: one page id per chunk. hipcc puts a branch
+    // and a full wait around every guarded load (20 serial latencies), so no
+    // load is guarded: in the one wave per round that straddles plen, a
+    // timestep >= plen re-reads row plen-1 of the sequence (always a valid
+    // row, and a page id inside the table), is scored -1e30 below and weighs
+    // exactly 0.
+    const int tlast = plen - 1;
+    // paged: the round's four page ids, loaded a round ahead as in
+    // k_attn_split; the first round's here, ahead of the loop, where the four
+    // issue together (inside it each lookup was a load and a full wait)
+    [[maybe_unused]] int pg[4];
+    if constexpr (ROWS::kPaged) {
+        #pragma unroll
+        for (int u = 0; u < 4; u++)
+            pg[u] = rows.seq_pages(b)[min(wave * 16 + u * 4, tlast & ~3)
+                                      >> rows.shift];
+    }
+
+    // a wave whose first timestep is at or past plen never enters: it keeps
+    // m = -1e30, l = 0, o = 0 and weighs nothing in the merge
+    for (int tb = wave * 16; tb < plen; tb += 16 * NW) {
+        int trow[4];      // the chunk's first t, clamped to the last chunk
+        int64_t roff[4];  // wave-uniform: where that row's head starts
+        #pragma unroll
+        for (int u = 0; u < 4; u++) {
+            trow[u] = min(tb + u * 4, tlast & ~3);
+            int64_t r = trow[u];  // kc / vc start at the row's sequence
+            if constexpr (ROWS::kPaged)
+                r = ((int64_t)pg[u] << rows.shift)
+                  + (trow[u] & ((1 << rows.shift) - 1));
+            roff[u] = r * kv_dim0 + kv_off;
+        }
+        // all loads of the round, K then V, before anything waits on one
+        KPack kk[4];
+        #pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int g = min(trow[u] + group, tlast) - trow[u];
+            kk[u] = *reinterpret_cast<const KPack *>(
+                kc + roff[u] + (g * kv_dim0 + lane16 * VEC16));
+        }
+        #define X(u, g) \
+            const VPack v##u##g = load_in_order(reinterpret_cast<const VPack *>( \
+                vc + roff[u] + (min(trow[u] + g, tlast) - trow[u]) * kv_dim0 \
+                + lane * VEC));
+        ATTN_WIDE_ROWS(X)
+        #undef X
+        // nothing moves across this: the V loads stay above the first K wait
+        __builtin_amdgcn_sched_barrier(0);
+
+        float s16[16];
+        float mn = m;
+        #pragma unroll
+        for (int u = 0; u < 4; u++) {
+            float partial = 0.0f;
             #pragma unroll
-            for (int v = 0; v < VEC; v++) {
-                const int i = lane * VEC + v;
-                vv[v] = (so[0][i] + so[1][i] + so[2][i] + so[3][i]) * invL;
-            }
-            if constexpr (VEC == 2) {
-                // lane holds elems (2*lane, 2*lane+1): block = 16-lane group,
-                // two values per lane — not the one-per-lane q80_quant_group32
-                const float amax = group16_reduce_max(fmaxf(fabsf(vv[0]), fabsf(vv[1])));
-                const float dd = amax / 127.0f;
-                const float qinv = dd > 0.0f ? 1.0f / dd : 0.0f;
-                const float q0 = rintf(vv[0] * qinv), q1 = rintf(vv[1] * qinv);
-                const int64_t obase = ((int64_t)b * n_heads0 + h0) * hd + lane * 2;
-                zq[obase] = (int8_t)q0;
-                zq[obase + 1] = (int8_t)q1;
-                const float bsum = group16_reduce_sum(q0 + q1);
-                if ((lane & 15) == 0) {
-                    const int blk = (h0 * hd + lane * 2) / QB;
-                    zs[(int64_t)b * (n_heads0 * hd / QB) + blk] = dd;
-                    zbs[(int64_t)b * (n_heads0 * hd / QB) + blk] = bsum;
-                }
-            } else {
-                const Q80Lane c = q80_quant_group32(vv[0]);
-                zq[((int64_t)b * n_heads0 + h0) * hd + lane] = (int8_t)c.qf;
-                const float bsum = group32_reduce_sum(c.qf);
-                if ((lane & 31) == 0) {
-                    const int blk = (h0 * hd + lane) / QB;
-                    zs[(int64_t)b * (n_heads0 * hd / QB) + blk] = c.d;
-                    zbs[(int64_t)b * (n_heads0 * hd / QB) + blk] = bsum;
-                }
-            }
-        } else {
-            if (lane == 0) {
-                ml_scratch[slot * 2] = M;
-                ml_scratch[slot * 2 + 1] = L;
-            }
+            for (int v = 0; v < VEC16; v++)
+                partial = fmaf(qreg[v], kv_f(kk[u].e[v]), partial);
+            const float su = group16_reduce_sum(partial) * scale;
             #pragma unroll
-            for (int v = 0; v < VEC; v++) {
-                const int i = lane * VEC + v;
-                o_scratch[slot * hd + i] = so[0][i] + so[1][i] + so[2][i] + so[3][i];
+            for (int gg = 0; gg < 4; gg++) {
+                float v = __shfl(su, gg * 16, WAVE);
+                if (tb + u * 4 + gg >= plen) v = -1e30f;
+                s16[4 * u + gg] = v;
+                mn = fmaxf(mn, v);
             }
+        }
+        // tb < plen: the round has a valid timestep, so mn is a real score
+        // and a masked one weighs exp(-1e30 - mn) = 0
+        const float f = __expf(m - mn);
+        float w16[16];
+        float lsum = 0.0f;
+        #pragma unroll
+        for (int i = 0; i < 16; i++) {
+            w16[i] = __expf(s16[i] - mn);
+            lsum += w16[i];
+        }
+        l = l * f + lsum;
+        #pragma unroll
+        for (int v = 0; v < VEC; v++) o[v] *= f;
+        #define X(u, g) \
+            _Pragma("unroll") \
+            for (int v = 0; v < VEC; v++) \
+                o[v] = fmaf(w16[4 * u + g], kv_f(v##u##g.e[v]), o[v]);
+        ATTN_WIDE_ROWS(X)
+        #undef X
+        m = mn;
+        if constexpr (ROWS::kPaged) {
+            #pragma unroll
+            for (int u = 0; u < 4; u++)
+                pg[u] = rows.seq_pages(b)[min(tb + 16 * NW + u * 4, tlast & ~3)
+                                          >> rows.shift];
         }
     }
 
+    // merge the 16 waves: one barrier, then hd threads each sum the 16
+    // partials of one output element
+    __shared__ float sm[NW], sl[NW];
+    __shared__ float so[NW][hd];
+    if (lane == 0) { sm[wave] = m; sl[wave] = l; }
+    #pragma unroll
+    for (int v = 0; v < VEC; v++) so[wave][lane * VEC + v] = o[v];
+    __syncthreads();
+    if (threadIdx.x >= hd) return;
+    const int i = threadIdx.x;
+    float M = -1e30f;
+    #pragma unroll
+    for (int w = 0; w < NW; w++) M = fmaxf(M, sm[w]);
+    // wave 0 always has timestep 0, so M is a real score; an empty wave has
+    // l = 0 and o = 0 and a weight of exp(-1e30 - M) = 0
+    float L = 0.0f, acc = 0.0f;
+    #pragma unroll
+    for (int w = 0; w < NW; w++) {
+        const float fw = __expf(sm[w] - M);
+        L = fmaf(sl[w], fw, L);
+        acc = fmaf(so[w][i], fw, acc);
+    }
+    // the Q80 triple of the head: thread i holds element i, so a block is a
+    // 32-lane group (hd threads = whole waves: every lane of it is here)
+    const Q80Lane c = q80_quant_group32(acc * (1.0f / L));
+    zq[((int64_t)b * n_heads0 + h0) * hd + i] = (int8_t)c.qf;
+    const float bsum = group32_reduce_sum(c.qf);
+    if ((i & 31) == 0) {
+        const int blk = (h0 * hd + i) / QB;
+        zs[(int64_t)b * (n_heads0 * hd / QB) + blk] = c.d;
+        zbs[(int64_t)b * (n_heads0 * hd / QB) + blk] = bsum;
+    }
 }
+#undef ATTN_WIDE_ROWS
 
 // GQA-grouped split variant: one workgroup owns ALL kv_mul query heads of
 // a kv head (wave w = query head kvh*kv_mul+w), so the K/V rows stream
@@ -671,16 +837,15 @@ static PagedRows paged_rows(const torch::Tensor &rows,
     return PagedRows{t.rows, page_table.data_ptr<int>(), shift};
 }
 
-// Split + combine launches of attention, for any row addressing. The
-// GQA-grouped experiment and the S==1 fused kernel (allow_variants) exist
-// for the single-sequence form only.
+// The launches of attention, for any row addressing: the wide single kernel
+// when splits == 1 and the output is the Q80 triple, else split + combine.
+// The GQA-grouped experiment exists for the single-sequence form only.
 template <typename ROWS>
 static void attn_launch(torch::Tensor &q, int64_t q_ld, torch::Tensor &kc,
                         torch::Tensor &vc, torch::Tensor &y, ROWS rows,
                         int64_t batch, int64_t n_heads0, int64_t kv_mul,
                         int64_t head_dim, int64_t splits,
                         torch::Tensor &ml_scratch, torch::Tensor &o_scratch,
-                        int *counter, bool allow_variants,
                         c10::optional<torch::Tensor> &zq,
                         c10::optional<torch::Tensor> &zs,
                         c10::optional<torch::Tensor> &zbs) {
@@ -702,28 +867,23 @@ static void attn_launch(torch::Tensor &q, int64_t q_ld, torch::Tensor &kc,
     // more than the saved traffic. Kept behind DLLAMA_GQA_ATTN=1.
     static const bool env_gqa =
         std::getenv("DLLAMA_GQA_ATTN") && atoi(std::getenv("DLLAMA_GQA_ATTN")) == 1;
-    const bool gqa = allow_variants && env_gqa && kv_mul > 1 && kv_mul <= 8
-        && n_heads0 % kv_mul == 0 && splits > 1;
-    // splits==1 + quant output: single fused kernel (normalize + Q80 emit
-    // in the split kernel), no combine launch
-    const bool fused = allow_variants && !gqa && splits == 1 && quant;
+    const bool gqa = std::is_same_v<ROWS, SeqRows> && env_gqa && kv_mul > 1
+        && kv_mul <= 8 && n_heads0 % kv_mul == 0 && splits > 1;
+    // splits==1 + quant output: the wide kernel normalizes and emits the Q80
+    // triple itself, no scratch and no combine launch
+    const bool wide = splits == 1 && quant;
     with_head_vec(head_dim, [&](auto vec_const) {
         constexpr int V = decltype(vec_const)::value;
         with_kv_ptrs(kc, vc, [&](auto *kcp, auto *vcp) {
             using KVT = std::remove_pointer_t<decltype(kcp)>;
-            auto split = [&](auto fuse_const) {
-                constexpr bool FUSE = decltype(fuse_const)::value;
-                hipLaunchKernelGGL((k_attn_split<V, KVT, FUSE, ROWS>), grid,
-                                   dim3(256), 0,
-                                   cur_stream(), q.data_ptr<float>(), (int)q_ld,
-                                   kcp, vcp, rows,
-                                   (int)n_heads0, (int)kv_mul, kv_dim0, scale,
-                                   ml_scratch.data_ptr<float>(),
-                                   o_scratch.data_ptr<float>(),
-                                   counter, nullptr,
-                                   FUSE ? zqp : nullptr, FUSE ? zsp : nullptr,
-                                   FUSE ? zbsp : nullptr);
-            };
+            if (wide) {
+                hipLaunchKernelGGL((k_attn_wide<V, KVT, ROWS>), cgrid,
+                                   dim3(1024), 0, cur_stream(),
+                                   q.data_ptr<float>(), (int)q_ld, kcp, vcp,
+                                   rows, (int)n_heads0, (int)kv_mul, kv_dim0,
+                                   scale, zqp, zsp, zbsp);
+                return;
+            }
             if constexpr (std::is_same_v<ROWS, SeqRows>) {
                 if (gqa) {
                     hipLaunchKernelGGL((k_attn_split_gqa<V, KVT>),
@@ -736,14 +896,15 @@ static void attn_launch(torch::Tensor &q, int64_t q_ld, torch::Tensor &kc,
                                        o_scratch.data_ptr<float>());
                     return;
                 }
-                if (fused) {
-                    split(std::true_type{});
-                    return;
-                }
             }
-            split(std::false_type{});
+            hipLaunchKernelGGL((k_attn_split<V, KVT, ROWS>), grid, dim3(256),
+                               0, cur_stream(), q.data_ptr<float>(), (int)q_ld,
+                               kcp, vcp, rows,
+                               (int)n_heads0, (int)kv_mul, kv_dim0, scale,
+                               ml_scratch.data_ptr<float>(),
+                               o_scratch.data_ptr<float>());
         });
-        if (fused) return;
+        if (wide) return;
         auto combine = [&](auto quant_const) {
             hipLaunchKernelGGL((k_attn_combine<V, decltype(quant_const)::value>),
                                cgrid, dim3(V * WAVE), 0, cur_stream(),
@@ -759,17 +920,17 @@ static void attn_launch(torch::Tensor &q, int64_t q_ld, torch::Tensor &kc,
 void attn(torch::Tensor q, int64_t q_ld, torch::Tensor kc, torch::Tensor vc,
           torch::Tensor y, torch::Tensor pos, int64_t batch, int64_t n_heads0,
           int64_t kv_mul, int64_t head_dim, int64_t splits,
-          torch::Tensor ml_scratch, torch::Tensor o_scratch, torch::Tensor counter,
+          torch::Tensor ml_scratch, torch::Tensor o_scratch,
+          torch::Tensor /*counter: unused, kept for the binding signature*/,
           c10::optional<torch::Tensor> zq = c10::nullopt,
           c10::optional<torch::Tensor> zs = c10::nullopt,
           c10::optional<torch::Tensor> zbs = c10::nullopt) {
     attn_launch(q, q_ld, kc, vc, y, SeqRows{pos.data_ptr<int>()}, batch,
                 n_heads0, kv_mul, head_dim, splits, ml_scratch, o_scratch,
-                counter.data_ptr<int>(), true, zq, zs, zbs);
+                zq, zs, zbs);
 }
 
-// Row b attends over cache rows base_b .. base_b+pos_b of the row table;
-// always the split + combine pair.
+// Row b attends over cache rows base_b .. base_b+pos_b of the row table.
 void attn_rows(torch::Tensor q, int64_t q_ld, torch::Tensor kc, torch::Tensor vc,
                torch::Tensor y, torch::Tensor rows, int64_t batch,
                int64_t n_heads0, int64_t kv_mul, int64_t head_dim,
@@ -778,8 +939,7 @@ void attn_rows(torch::Tensor q, int64_t q_ld, torch::Tensor kc, torch::Tensor vc
                c10::optional<torch::Tensor> zs = c10::nullopt,
                c10::optional<torch::Tensor> zbs = c10::nullopt) {
     attn_launch(q, q_ld, kc, vc, y, table_rows(rows, batch), batch, n_heads0,
-                kv_mul, head_dim, splits, ml_scratch, o_scratch, nullptr,
-                false, zq, zs, zbs);
+                kv_mul, head_dim, splits, ml_scratch, o_scratch, zq, zs, zbs);
 }
 
 // attn_rows over a paged cache: row b attends over positions 0..pos_b of its
@@ -795,7 +955,7 @@ void attn_paged(torch::Tensor q, int64_t q_ld, torch::Tensor kc, torch::Tensor v
     attn_launch(q, q_ld, kc, vc, y,
                 paged_rows(rows, page_table, page_size, batch, kc), batch,
                 n_heads0, kv_mul, head_dim, splits, ml_scratch, o_scratch,
-                nullptr, false, zq, zs, zbs);
+                zq, zs, zbs);
 }
 
 template <typename ROWS>

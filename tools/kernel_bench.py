@@ -1,6 +1,6 @@
 """Per-kernel microbench on Llama-3.1-8B decode shapes (isolated graphs)."""
-import sys, time, torch
-sys.path.insert(0, "/root/repo")
+import os, statistics, sys, time, torch
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from dllama_amd.ops import hip_ops
 
 k = hip_ops()
@@ -22,6 +22,49 @@ def bench(fn, n=256, reps=10):
     for _ in range(reps): gr.replay()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / reps / n * 1e6
+
+def attn_ab(positions=(32, 128, 250, 500, 1000), rounds=5):
+    """Short-context attention alone in an isolated hipGraph at 8B shapes
+    (32 heads, kv_mul 4, hd 128, f16 KV, Q80 output): the split + combine
+    pair at S=8 and S=16 against the single S=1 launch. S=1 is the wide
+    16-wave kernel in this tree; run this file from a checkout of an older
+    commit to time the 4-wave fused kernel it replaced. The candidates are
+    interleaved over `rounds`; median and min us per call.
+
+      python tools/kernel_bench.py attn     this section alone"""
+    H0, hd, kvd, seq, kv_mul = 32, 128, 1024, 2048, 4
+    kc = (torch.randn(seq, kvd, device=dev, generator=g) * 0.3).half()
+    vc = torch.randn(seq, kvd, device=dev, generator=g).half()
+    qv = torch.randn(1, H0 * hd, device=dev, generator=g)
+    y = torch.zeros(1, H0 * hd, device=dev)
+    zq = torch.zeros(1, H0 * hd, dtype=torch.int8, device=dev)
+    zs = torch.zeros(1, H0 * hd // 32, device=dev)
+    zbs = torch.zeros(1, H0 * hd // 32, device=dev)
+    cnt = torch.zeros(H0, dtype=torch.int32, device=dev)
+    cands = (("pair S=8", 8), ("pair S=16", 16), ("single S=1", 1))
+    scr = {S: (torch.zeros(H0 * S * 2, device=dev),
+               torch.zeros(H0 * S * hd, device=dev)) for _, S in cands}
+    print("\n-- attention, isolated graph, 8B shapes, f16 KV, Q80 out "
+          "(us per call: median / min) --")
+    for p in positions:
+        pos = torch.tensor([p], dtype=torch.int32, device=dev)
+        times = {name: [] for name, _ in cands}
+        for _ in range(rounds):
+            for name, S in cands:
+                ml, osc = scr[S]
+                times[name].append(bench(
+                    lambda: k.attn(qv, H0 * hd, kc, vc, y, pos, 1, H0, kv_mul,
+                                   hd, S, ml, osc, cnt, zq, zs, zbs),
+                    n=128, reps=5))
+        print(f"pos={p:5d}  " + "  ".join(
+            f"{name}: {statistics.median(t):6.2f} / {min(t):6.2f}"
+            for name, t in times.items()))
+
+
+if sys.argv[1:] == ["attn"]:
+    attn_ab()
+    sys.exit(0)
+
 
 def mklin(d, n):
     qs = torch.randint(0, 256, (d, n // 2), dtype=torch.uint8, device=dev, generator=g)
@@ -134,3 +177,5 @@ for d, n, ks, tag in ((1536, 2048, 8, "w13"), (2048, 768, 1, "w2")):
     ideal = (8 * d * n * 0.5625) / 6.3e3 / 1000
     print(f"grouped {tag:4s} v1={t1:7.2f}us v2={t2:7.2f}us ideal={ideal:6.2f}us "
           f"v2-eff={100*ideal/t2:4.0f}%")
+
+attn_ab()

@@ -10,6 +10,17 @@ waves/SIMD ~= 512 // (vgpr+agpr rounded up to 8), capped at 8 by LDS
 (160 KB/CU) and workgroup shape.
 
 Usage: python tools/kernel_resources.py [path/to/lib.so]
+
+Manual check after a compiler upgrade (no test sees it: every result stays
+right, only the latency comes back): `k_attn_wide` must issue all loads of
+a round before its first wait. Disassemble the code objects
+(`llvm-objdump -d` on what extract_hsacos() returns, or hipcc `-S
+--cuda-device-only` on csrc/attn.hip) and read `k_attn_wide<2, __half,
+SeqRows>`: 2 q loads, then inside the loop 4 `global_load_dwordx4` (K) and
+16 `global_load_dword` (V) with no `s_waitcnt vmcnt` between them, then
+`; sched_barrier`, then the first wait, `s_waitcnt vmcnt(19)`. A
+`vmcnt(0)` between the loads, or V loads below the barrier, is the serial
+form that profiles/r07_wide_attention.md describes (4.4 -> 14 us).
 """
 
 import re
