@@ -2,6 +2,11 @@
 
 #include "dllama_common.h"
 
+#include <atomic>
+#include <mutex>
+#include <unordered_map>
+#include <vector>
+
 // ------------------------------------------------------------------ Q40 GEMV
 // y[b, row] = sum_j w[row, j] * x[b, j]  with W in Q40 planes and x in Q80.
 // One wave per output row; lane l streams block l, l+64, ... of the row.
@@ -32,12 +37,41 @@ __device__ __forceinline__ int q40_block_dot(const uint4 wq, const int4 x0,
                        // the all-gather payload) straight from the epilogue
 #define EPI_RESID_Q 3  // EPI_RESID + deferred-scale Q80 emit of x*wnorm (one
                        // block per 16-wave wg; consumer applies inv_rms, PRO==2)
+#define EPI_RESID_QH 5 // EPI_RESID_Q on 4- or 8-wave wgs: the 16/wpb wgs of a
+                       // 32-row block hand their rows to the last arriver,
+                       // which emits the block (see the hand-off notes below)
 #define EPI_RESID 1  // x[b,row] += v; accumulate sum(x'^2) into 16-way-spread
                      //  slots -> the next norm becomes a single wide pass
 #define EPI_ROPE 2   // llama rope: rows (2j,2j+1) are a rotation pair held by
                      //  one RPW=2 wave; q rotated into y, k rotated into the
                      //  KV cache, v copied into the cache
 
+// EPI_RESID_Q assembles the next matmul's Q80 block in workgroup-local LDS,
+// so its workgroup must own the block's 32 rows: 16 waves x RPW 2, 128
+// workgroups at d = 4096 on 256 CUs. EPI_RESID_QH computes the same values
+// on the production shape (4 or 8 waves x RPW 2, 8 or 16 rows per wg) and
+// hands the rows over inside the launch: the wg that arrives last at the
+// block's ticket quantizes all 32 rows. Each row is folded by one wave with
+// the 16-wave form's lane partition and summation order, so x and the Q80
+// triple are bit-identical; ssq differs by the order of its float atomics.
+// The hand-off has three rules, and the kernel is wrong without any of them:
+//  1. sc1 on both sides. x_resid is stored write-through (agent-scope
+//     relaxed atomic store = global_store_dwordx2 sc1) and the last arriver
+//     reads all 32 rows with agent-scope relaxed atomic loads
+//     (global_load_dword sc1), which bypass its CU's L1. That L1 holds the
+//     neighbours' OLD values: the wg read its own rows of the same 128-byte
+//     lines when it folded the residual. No release/acquire fence is needed,
+//     only a wavefront-scope fence to pin the order for the compiler.
+//  2. drain before the ticket. Every storing wave runs s_waitcnt vmcnt(0)
+//     after its stores, then the wg's barrier, then ONE thread adds to the
+//     ticket (agent-scope relaxed fetch_add).
+//  3. nobody waits. A wg that is not last exits; no wg polls, spins or
+//     sleeps. A launch in which an arrival never comes leaves a stale Q80
+//     block; it cannot hang.
+// The last arriver stores 0 to the ticket (every arrival has been counted by
+// then), so each completed launch leaves the tickets at rest and replays
+// need no reset node. Tickets: see resid_q_tickets().
+//
 // RPW = rows per wave: processing 2 rows per wave doubles the independent
 // 16B weight loads in flight per lane (the decode GEMV is HBM-latency
 // limited at 1 row/wave). NB = batch columns. PRO = 0: plain Q80 input;
@@ -94,6 +128,24 @@ __global__ void k_q40_gemv(const uint8_t *__restrict__ qs,
     for (int r = 0; r < RPW; r++)
         #pragma unroll
         for (int b = 0; b < NB; b++) acc[r][b] = 0.0f;
+
+    // EPI_RESID_QH (B=1, RPW=2, d % 32 == 0 so every wave owns two valid
+    // rows): lane 0 fetches the wave's residual values ahead of the weight
+    // stream, so the fold at the tail does not start with a load from
+    // memory. A relaxed atomic load of wavefront scope is an ordinary
+    // global_load that hipcc keeps in program order (a plain load is sunk
+    // to its use).
+    static_assert(EPI != EPI_RESID_QH || (RPW == 2 && NB == 1),
+                  "the hand-off epilogue is B=1, RPW=2");
+    [[maybe_unused]] float xres[2] = {0.0f, 0.0f};
+    if constexpr (EPI == EPI_RESID_QH) {
+        if (lane == 0) {
+            #pragma unroll
+            for (int r = 0; r < 2; r++)
+                xres[r] = __hip_atomic_load(&x_resid[rbase + r], __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_WAVEFRONT);
+        }
+    }
 
     for (int jp = j0p + lane; jp < j1p; jp += WAVE) {
         const int j = jp << 1;
@@ -197,6 +249,22 @@ __global__ void k_q40_gemv(const uint8_t *__restrict__ qs,
                     if (RPW == 2) vc[(int64_t)pb * kv_dim0 + rv + 1] = v[1 % RPW];
                 }
             }
+        } else if constexpr (EPI == EPI_RESID_QH) {
+            // residual fold of the wave's row pair (fetched ahead of the
+            // stream), stored write-through (sc1) for the block's last
+            // arriver (hand-off rule 1) as ONE 8-byte store. With a load,
+            // a wait and a 4-byte store per row the launch was 1.4 us
+            // slower: stores count in vmcnt on this target, so the wait for
+            // the second row's load also sat out the first store's trip to
+            // memory (profiles/r08_resid_q_handoff.md)
+            const float xv0 = xres[0] + v[0];
+            const float xv1 = xres[1] + v[1 % RPW];
+            ssq_local[b] += xv0 * xv0;
+            ssq_local[b] += xv1 * xv1;
+            const unsigned long long pk = (unsigned long long)__float_as_uint(xv0)
+                | ((unsigned long long)__float_as_uint(xv1) << 32);
+            __hip_atomic_store(reinterpret_cast<unsigned long long *>(x_resid + rbase),
+                               pk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else {
             #pragma unroll
             for (int r = 0; r < RPW; r++) {
@@ -222,6 +290,9 @@ __global__ void k_q40_gemv(const uint8_t *__restrict__ qs,
             }
         }
     }
+    // amax_scratch has a second tenant: EPI_RESID_QH receives its uint32
+    // block tickets in it (see that epilogue). The argmax below must stay
+    // EPI_NONE-only so that the two never meet.
     if (EPI == EPI_NONE && NB == 1 && amax_scratch != nullptr) {
         // stage 1 of the greedy argmax: one packed best per workgroup
         __shared__ unsigned long long wb[16];
@@ -261,6 +332,48 @@ __global__ void k_q40_gemv(const uint8_t *__restrict__ qs,
             if (threadIdx.x == 0) {
                 oqs[blockIdx.x] = c.d;
                 oqbs[blockIdx.x] = bsq;
+            }
+        }
+    }
+    if constexpr (EPI == EPI_RESID_QH) {
+        // rule 2: every wave drains its write-through stores, then the barrier
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __shared__ float sredq[8];
+        __shared__ unsigned slast;
+        if (lane == 0) sredq[wid] = wave_valid ? ssq_local[0] : 0.0f;
+        __syncthreads();
+        // the tickets ride in the argmax-scratch argument, which this
+        // epilogue has no other use for: the kernel's argument list, and
+        // with it every other instantiation, stays what it was
+        unsigned *tickets = reinterpret_cast<unsigned *>(amax_scratch);
+        const unsigned per = 16u / (unsigned)wpb;  // arrivals per 32-row block
+        const unsigned blk = blockIdx.x / per;
+        if (threadIdx.x == 0) {
+            float t = 0.0f;
+            for (int wv = 0; wv < wpb; wv++) t += sredq[wv];
+            const unsigned prev = __hip_atomic_fetch_add(
+                tickets + blk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            // behind the ticket: its return is not held up by this one
+            atomicAdd(ssq_slot(ssq, 0, blockIdx.x), t);
+            const unsigned last = prev == per - 1u;
+            if (last)  // all arrivals counted: back to the rest state
+                __hip_atomic_store(tickets + blk, 0u, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+            slast = last;
+        }
+        __syncthreads();
+        if (!slast) return;  // rule 3: not last -> done, nobody waits
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (threadIdx.x < 32 && (int)(blk * 32 + threadIdx.x) < d) {
+            const int row = blk * 32 + threadIdx.x;
+            const float xv = __hip_atomic_load(&x_resid[row], __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT);
+            const Q80Lane c = q80_quant_group32(xv * wnorm[row]);
+            oqq[blk * QB + threadIdx.x] = (int8_t)c.qf;
+            const float bsq = group32_reduce_sum(c.qf);
+            if (threadIdx.x == 0) {
+                oqs[blk] = c.d;
+                oqbs[blk] = bsq;
             }
         }
     }
@@ -590,6 +703,9 @@ struct GemvEpi {
     int8_t *oqq = nullptr;
     float *oqs = nullptr;
     float *oqbs = nullptr;
+    // EPI_RESID_QH: waves per workgroup (4 or 8); its block tickets travel
+    // in `slot`
+    int waves = 0;
 };
 
 // rows per wave of the batch-1 GEMV over d rows: RPW=2 halves the wave count
@@ -609,8 +725,10 @@ static void gemv_launch(torch::Tensor &qs, torch::Tensor &scales, torch::Tensor 
     const int n = qs.size(1) * 2;
     TORCH_CHECK(xq.size(-1) == n, "x width mismatch");
     TORCH_CHECK(n % QB == 0, "n must be a multiple of 32");
-    // EPI_RESID_Q / EPI_PACK: 16 waves x RPW2 = 32 rows per wg = one block
-    const int waves_per_block = (EPI == EPI_RESID_Q || EPI == EPI_PACK) ? 16 : 4;
+    // EPI_RESID_Q / EPI_PACK: 16 waves x RPW2 = 32 rows per wg = one block;
+    // EPI_RESID_QH: 4 or 8 waves, chosen by the caller (resid_q_waves)
+    const int waves_per_block = (EPI == EPI_RESID_QH) ? e.waves
+        : (EPI == EPI_RESID_Q || EPI == EPI_PACK) ? 16 : 4;
     const dim3 block(waves_per_block * WAVE);
     auto launch = [&](auto nb_const, auto rpw_const) {
         constexpr int RPW = decltype(rpw_const)::value;
@@ -635,7 +753,12 @@ static void gemv_launch(torch::Tensor &qs, torch::Tensor &scales, torch::Tensor 
     // dead RPW combinations (that additionally spill) alive
     auto launch_nb = [&](auto nb_const) {
         constexpr int NB = decltype(nb_const)::value;
-        if constexpr (EPI == EPI_ROPE || NB == 2 || NB == 4) {
+        if constexpr (EPI == EPI_RESID_QH) {
+            // B=1, RPW=2 only: the row-pair fold and the block/ticket
+            // arithmetic assume it
+            if constexpr (NB == 1) launch(nb_const, r2);
+            else TORCH_CHECK(false, "resid_q hand-off form is batch 1 only");
+        } else if constexpr (EPI == EPI_ROPE || NB == 2 || NB == 4) {
             launch(nb_const, r2);
         } else if constexpr (NB > 4) {
             launch(nb_const, r1);
@@ -722,16 +845,88 @@ void add_ssq_q(torch::Tensor x, torch::Tensor parts, torch::Tensor ssq,
                        obs.data_ptr<float>(), n, (int)nks);
 }
 
+// waves per workgroup of the resid_q down-projection over a [d, n] matrix:
+// 16 = one block per wg (EPI_RESID_Q), 4 / 8 = the hand-off form
+// (EPI_RESID_QH) with four / two arrivals per block. DLLAMA_RESID_Q_WAVES
+// (4, 8 or 16, read once) forces one form for A/B runs and the equality
+// test; q40_gemv_resid_q_waves() does the same from inside a process.
+// Default rule, from the isolated out-of-cache timings of
+// `tools/kernel_bench.py resid` (profiles/r08_resid_q_handoff.md): the
+// hand-off's tail costs more than the fuller chip gives back unless a row is
+// long. 8 waves won at every measured shape with n >= 8192 and d < 8192
+// (8B w2 12.8 -> 10.3 us, 1B/3B w2 -0.3..-0.5 us) and beat 4 waves there;
+// 16 waves won at every n <= 4096 (by 0.5..0.8 us) and at d = 8192.
+// q40_gemv_resid_q_waves() is process-global and meant for the tests and
+// tools/kernel_bench.py only: whoever sets it puts it back to 0.
+static std::atomic<int> g_resid_q_waves_override{0};
+
+static int resid_q_waves(int d, int n) {
+    static const int env_waves =
+        std::getenv("DLLAMA_RESID_Q_WAVES") ? atoi(std::getenv("DLLAMA_RESID_Q_WAVES")) : 0;
+    const int ov = g_resid_q_waves_override.load();
+    const int forced = ov ? ov : env_waves;
+    if (forced == 4 || forced == 8 || forced == 16) return forced;
+    return (d < 8192 && n >= 8192) ? 8 : 16;
+}
+
+void q40_gemv_resid_q_waves(int64_t waves) {
+    TORCH_CHECK(waves == 0 || waves == 4 || waves == 8 || waves == 16,
+                "resid_q waves: 0 (default rule), 4, 8 or 16");
+    g_resid_q_waves_override.store((int)waves);
+}
+
+// EPI_RESID_QH tickets: one uint32 per 32-row block, at rest 0. Owned here
+// and keyed by the residual buffer's address: two launches that may be in
+// flight at once never share x, so they never share tickets, and the
+// binding needs no new argument. An array is allocated and zeroed at the
+// first launch on its x, which must be outside stream capture (every
+// capture in this project follows eager warm-ups of the same calls); a
+// captured graph then names memory that is never freed: entries are kept
+// for the life of the process (4 bytes per block per distinct x address;
+// a reused address finds its old tickets, at rest).
+static unsigned *resid_q_tickets(const torch::Tensor &x, int nblocks) {
+    static std::mutex mu;
+    // leaked on purpose: no device free during static destruction
+    static auto *store = new std::unordered_map<const void *, torch::Tensor>();
+    static auto *outgrown = new std::vector<torch::Tensor>();
+    std::lock_guard<std::mutex> lock(mu);
+    const void *key = x.data_ptr();
+    auto it = store->find(key);
+    if (it != store->end() && it->second.numel() >= nblocks)
+        return reinterpret_cast<unsigned *>(it->second.data_ptr<int32_t>());
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    C10_HIP_CHECK(hipStreamIsCapturing(cur_stream(), &st));
+    TORCH_CHECK(st == hipStreamCaptureStatusNone,
+                "q40_gemv_resid_q: first use of this residual buffer (or with "
+                "a larger d) inside stream capture; run the call eagerly once "
+                "before capturing so its block tickets exist");
+    torch::Tensor t = torch::zeros({nblocks}, x.options().dtype(torch::kInt32));
+    // zeroed on this stream; make it hold for a later launch on any stream
+    C10_HIP_CHECK(hipStreamSynchronize(cur_stream()));
+    if (it != store->end()) {
+        outgrown->push_back(it->second);  // a graph may still name it
+        it->second = t;
+    } else {
+        store->emplace(key, t);
+    }
+    return reinterpret_cast<unsigned *>(t.data_ptr<int32_t>());
+}
+
 void q40_gemv_resid_q(torch::Tensor qs, torch::Tensor scales, torch::Tensor xq,
                       torch::Tensor xs, torch::Tensor xbs, torch::Tensor x,
                       torch::Tensor ssq, torch::Tensor wnorm, torch::Tensor oq,
                       torch::Tensor os, torch::Tensor obs) {
     // decode down-projection with fused residual + ssq + DEFERRED Q80 emit
     // of x*wnorm: replaces gemv_resid + norm_quant (the consumer runs with
-    // ssq_in to apply inv_rms). B=1 only; 16-wave wgs (one block per wg).
+    // ssq_in to apply inv_rms). B=1 only; 16-wave wgs (one block per wg) or
+    // the 4/8-wave hand-off form, see resid_q_waves().
     CHECK_CUDA(qs); CHECK_CONT(qs); CHECK_CONT(xq);
     const int d = qs.size(0);
     TORCH_CHECK(d % 32 == 0, "resid_q needs d % 32 == 0");
+    TORCH_CHECK(x.numel() >= d && wnorm.numel() >= d && oq.numel() >= d,
+                "resid_q: x, wnorm and oq need d elements");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr<float>()) % 8 == 0,
+                "resid_q: x must be 8-byte aligned (row pairs are stored whole)");
     GemvEpi e;
     e.x_resid = x.data_ptr<float>();
     e.ssq = ssq.data_ptr<float>();
@@ -740,7 +935,14 @@ void q40_gemv_resid_q(torch::Tensor qs, torch::Tensor scales, torch::Tensor xq,
     e.oqs = os.data_ptr<float>();
     e.oqbs = obs.data_ptr<float>();
     e.force_rpw2 = true;
-    gemv_launch<EPI_RESID_Q, 0>(qs, scales, xq, xs, xbs, x.data_ptr<float>(), 1, e);
+    const int waves = resid_q_waves(d, (int)qs.size(1) * 2);
+    if (waves == 16) {
+        gemv_launch<EPI_RESID_Q, 0>(qs, scales, xq, xs, xbs, x.data_ptr<float>(), 1, e);
+    } else {
+        e.waves = waves;
+        e.slot = reinterpret_cast<unsigned long long *>(resid_q_tickets(x, d / 32));
+        gemv_launch<EPI_RESID_QH, 0>(qs, scales, xq, xs, xbs, x.data_ptr<float>(), 1, e);
+    }
 }
 
 void q40_gemv_resid(torch::Tensor qs, torch::Tensor scales, torch::Tensor xq,
@@ -909,6 +1111,7 @@ void register_gemv(py::module &m) {
           py::arg("eps") = 0.0);
     m.def("q40_gemv_resid", &q40_gemv_resid);
     m.def("q40_gemv_resid_q", &q40_gemv_resid_q);
+    m.def("q40_gemv_resid_q_waves", &q40_gemv_resid_q_waves);
     m.def("q40_gemv_pack", &q40_gemv_pack);
     m.def("q40_gemv_ksplit", &q40_gemv_ksplit);
     m.def("add_ssq_q", &add_ssq_q);

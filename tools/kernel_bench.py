@@ -61,8 +61,77 @@ def attn_ab(positions=(32, 128, 250, 500, 1000), rounds=5):
             for name, t in times.items()))
 
 
+def resid_ab(rounds=5, forms=(16, 8, 4)):
+    """q40_gemv_resid_q alone in an isolated hipGraph at the down-projection
+    shapes (wo, w2) of the 1B, 3B, 8B and 70B presets, one column per
+    workgroup form: 16 waves (the block assembled in one workgroup's LDS)
+    and the 8- and 4-wave hand-off forms (last arriver emits the block),
+    forced through q40_gemv_resid_q_waves(). The forms are interleaved over
+    `rounds`; median / min us per call. Two figures per form:
+
+      hbm    the graph rotates over distinct weight copies that together
+             exceed 300 MB, more than the 256 MiB Infinity Cache holds, so
+             every launch streams its matrix from HBM as a decode step does
+      cache  one matrix replayed 64 times, served by the Infinity Cache
+
+      python tools/kernel_bench.py resid     this section alone"""
+    shapes = []
+    for tag, dim, ff in (("1b", 2048, 8192), ("3b", 3072, 8192),
+                         ("8b", 4096, 14336), ("70b", 8192, 28672)):
+        shapes += [(f"{tag} wo", dim, dim), (f"{tag} w2", dim, ff)]
+    print("\n-- q40_gemv_resid_q, isolated graph (us per call: median / min); "
+          "hbm = rotating >300 MB of weight copies, cache = one matrix --")
+    for tag, d, n in shapes:
+        nbytes = d * n * 0.5625
+        copies = int(300e6 // nbytes) + 1
+        qs = torch.randint(0, 256, (copies, d, n // 2), dtype=torch.uint8,
+                           device=dev, generator=g)
+        sc = (torch.rand((copies, d, n // 32), device=dev, generator=g)
+              * 0.01).to(torch.float16)
+        xq = torch.randint(-100, 100, (1, n), dtype=torch.int8, device=dev,
+                           generator=g)
+        xs = torch.rand(1, n // 32, device=dev, generator=g) * 0.01
+        xbs = torch.rand(1, n // 32, device=dev, generator=g)
+        xr = torch.zeros(1, d, device=dev)
+        sq = torch.zeros(16 * 32, device=dev)
+        wn = torch.rand(d, device=dev, generator=g)
+        oq = torch.zeros(1, d, dtype=torch.int8, device=dev)
+        os_ = torch.zeros(1, d // 32, device=dev)
+        obs = torch.zeros(1, d // 32, device=dev)
+        it = [0]
+
+        def rotating():
+            i = it[0] % copies
+            it[0] += 1
+            k.q40_gemv_resid_q(qs[i], sc[i], xq, xs, xbs, xr, sq, wn, oq, os_, obs)
+
+        def single():
+            k.q40_gemv_resid_q(qs[0], sc[0], xq, xs, xbs, xr, sq, wn, oq, os_, obs)
+
+        nrot = max(64, copies)
+        times = {(f, v): [] for f in forms for v in ("hbm", "cache")}
+        for _ in range(rounds):
+            for f in forms:
+                k.q40_gemv_resid_q_waves(f)
+                it[0] = 0
+                times[(f, "hbm")].append(bench(rotating, n=nrot, reps=5))
+                times[(f, "cache")].append(bench(single, n=64, reps=5))
+        k.q40_gemv_resid_q_waves(0)
+        ideal = nbytes / 6.3e3 / 1000  # us at 6.3 TB/s
+        print(f"{tag:7s} {d:5d}x{n:<5d} {nbytes / 1e6:6.1f} MB x{copies:<3d} "
+              f"ideal {ideal:5.2f} | " + " | ".join(
+                  f"{f:2d}w hbm {statistics.median(times[(f, 'hbm')]):6.2f} /"
+                  f" {min(times[(f, 'hbm')]):6.2f}"
+                  f" cache {statistics.median(times[(f, 'cache')]):6.2f} /"
+                  f" {min(times[(f, 'cache')]):6.2f}" for f in forms))
+        del qs, sc
+
+
 if sys.argv[1:] == ["attn"]:
     attn_ab()
+    sys.exit(0)
+if sys.argv[1:] == ["resid"]:
+    resid_ab()
     sys.exit(0)
 
 
@@ -179,3 +248,4 @@ for d, n, ks, tag in ((1536, 2048, 8, "w13"), (2048, 768, 1, "w2")):
           f"v2-eff={100*ideal/t2:4.0f}%")
 
 attn_ab()
+resid_ab()

@@ -21,6 +21,15 @@ SeqRows>`: 2 q loads, then inside the loop 4 `global_load_dwordx4` (K) and
 `; sched_barrier`, then the first wait, `s_waitcnt vmcnt(19)`. A
 `vmcnt(0)` between the loads, or V loads below the barrier, is the serial
 form that profiles/r07_wide_attention.md describes (4.4 -> 14 us).
+
+Second manual check: `k_q40_gemv<1, 2, 5, 0>` (the hand-off form of
+q40_gemv_resid_q) exchanges rows between workgroups of one launch. Expected
+here: 0 spill and no more VGPRs than `k_q40_gemv<1, 2, 1, 0>`. In its
+disassembly the store of x must be a `global_store_dwordx2 ... sc1`
+followed by `s_waitcnt vmcnt(0)` before the `s_barrier` in front of the
+ticket's `global_atomic_add`, the load of x after the second barrier a
+`global_load_dword ... sc1`, and the kernel must hold no `buffer_wbl2` and
+no `buffer_inv` (profiles/r08_resid_q_handoff.md).
 """
 
 import re
