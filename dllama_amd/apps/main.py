@@ -51,6 +51,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "--max-seq-len rows per slot")
     p.add_argument("--page-size", type=int, default=64,
                    help="rows per KV page (--kv-pages): a power of two, 4..256")
+    p.add_argument("--kv-dtype", default=None, choices=["f16", "f32", "q80"],
+                   help="KV cache format. HIP backend: f16 is the default "
+                        "(f32 under DLLAMA_KV_F32=1); q80 stores int8 codes + "
+                        "f16 block scales, 0.53x the bytes of f16. CPU "
+                        "backend: q80 round-trips K/V through Q80 blocks on "
+                        "their way into the f32 cache (the HIP oracle)")
     p.add_argument("--steps", type=int, default=64)
     p.add_argument("--buffer-float-type", default="q80", choices=["q80", "f32"],
                    help="TP sync buffer quantization (reference --buffer-float-type)")
@@ -120,12 +126,16 @@ def load_engine(args):
                 f"error: --page-size must be a power of two in 4..256 "
                 f"(got {page_size})")
     paging = dict(kv_pages=kv_pages, page_size=page_size) if kv_pages else {}
+    kv_dtype = getattr(args, "kv_dtype", None)
+    if kv_dtype is not None:  # the default passes nothing to the backend
+        paging["kv_dtype"] = kv_dtype
     sync = Q80 if args.buffer_float_type == "q80" else F32
     m = mf.ModelFile(args.model, max_seq_len=args.max_seq_len, sync_type=sync)
     use_gpu = torch.cuda.is_available() and args.gpu_index != -1
     cfg = ModelConfig.from_header(m.header, world=comm.world, rank=comm.rank)
     if comm.rank == 0:
-        _print_header(m.header, cfg, use_gpu, slots, kv_pages, page_size)
+        _print_header(m.header, cfg, use_gpu, slots, kv_pages, page_size,
+                      kv_dtype)
     if use_gpu:
         from ..models.hip_model import HipTransformer
         dev = args.gpu_index if args.gpu_index is not None \
@@ -172,7 +182,12 @@ def load_engine(args):
     return InferenceEngine(model, tok, sampler, n_batches=nb), m, comm
 
 
-def _print_header(h, cfg, use_gpu, slots=1, kv_pages=0, page_size=64):
+# bytes per cached K or V element: q80 = 32 int8 codes + one f16 scale
+KV_ELEM_BYTES = {"f32": 4.0, "f16": 2.0, "q80": 1.0 + 2.0 / 32}
+
+
+def _print_header(h, cfg, use_gpu, slots=1, kv_pages=0, page_size=64,
+                  kv_dtype=None):
     print(f"💡 Arch: {'Llama' if h.arch_type == mf.ARCH_LLAMA else 'Qwen3 MoE' if h.arch_type == mf.ARCH_QWEN3_MOE else 'Qwen3'}")
     print(f"💡 Dim: {h.dim}\n💡 HiddenDim: {h.hidden_dim}\n💡 nLayers: {h.n_layers}")
     print(f"💡 nHeads: {h.n_heads}\n💡 nKvHeads: {h.n_kv_heads}\n💡 HeadDim: {h.head_dim}")
@@ -191,6 +206,10 @@ def _print_header(h, cfg, use_gpu, slots=1, kv_pages=0, page_size=64):
     else:
         shape = (f"seq {cfg.seq_len}"
                  + (f" x {slots} slots)" if slots > 1 else ")"))
+    if kv_dtype is not None:
+        # --kv-dtype given: the bytes of that format, exactly, and its name
+        kv_bytes = int(kv_bytes // 4 * KV_ELEM_BYTES[kv_dtype])
+        shape = f"{kv_dtype}, {kv_bytes} bytes, {shape}"
     print(f"📀 Weights/rank: {weights / max(1, cfg.world) / 1e9:.2f} GB"
           f"  KV cache/rank: {kv_bytes / 1e9:.2f} GB ({shape}")
 

@@ -43,8 +43,12 @@ class CpuTransformer:
     def __init__(self, m: ModelFile, config: ModelConfig, comm: Comm | None = None,
                  activation_quant: bool = True, weight_dtype: torch.dtype = torch.float32,
                  n_slots: int = 1, n_batches: int = 32, kv_pages: int = 0,
-                 page_size: int = 64):
+                 page_size: int = 64, kv_dtype: str | None = None):
         self.cfg = config
+        # "q80": K and V are round-tripped through stored Q80 blocks (f16
+        # scale) where they enter the cache, which stays f32: the oracle of
+        # the HIP backend's Q80 KV cache. Any other value: the plain f32 cache.
+        self.kv_q80 = kv_dtype == "q80"
         if n_slots < 1:
             raise ValueError(f"n_slots must be >= 1 (got {n_slots})")
         # kv_pages > 0: the cache is a pool of kv_pages pages of page_size
@@ -234,6 +238,8 @@ class CpuTransformer:
                                c.norm_eps).reshape(B, -1)
             q = self._rope(q, positions)
             k = self._rope(k, positions)
+            if self.kv_q80:
+                k, v = R.q80_roundtrip_f16(k), R.q80_roundtrip_f16(v)
             self.k_cache[l, cache_rows] = k
             self.v_cache[l, cache_rows] = v
             if paged_slots is not None:

@@ -146,8 +146,12 @@ class HipTransformer:
 
     def __init__(self, config: ModelConfig, device=None, comm: Comm | None = None,
                  n_batches: int = 32, force_sync: bool = False,
-                 n_slots: int = 1, kv_pages: int = 0, page_size: int = 64):
+                 n_slots: int = 1, kv_pages: int = 0, page_size: int = 64,
+                 kv_dtype: str | None = None):
         self.cfg = c = config
+        if kv_dtype not in (None, "f16", "f32", "q80"):
+            raise ValueError(
+                f"kv_dtype must be 'f16', 'f32' or 'q80' (got {kv_dtype!r})")
         # KV slots: each layer's cache holds n_slots sequences of seq_len
         # rows; every single-sequence path lives in slot 0 (the first
         # seq_len rows), forward_rows addresses any of them
@@ -205,6 +209,17 @@ class HipTransformer:
         self.fused_rope = self.rope_style == 0 and not c.is_qwen3
         self.row_bytes = c.dim + 2 * (c.dim // QB)  # one Q80 wire row
         self._read_options()
+        # KV cache format: None = f16, or f32 under DLLAMA_KV_F32=1; an
+        # explicit value wins over the environment. "q80": int8 codes + f16
+        # block scales, 0.53x the bytes of f16 (docs/DESIGN.md §8).
+        self.kv_dtype = kv_dtype or ("f32" if self.kv_f32 else "f16")
+        self.kv_f32 = self.kv_dtype == "f32"
+        self.kv_q80 = self.kv_dtype == "q80"
+        if self.kv_q80:
+            # the GEMV rope epilogue holds two rows per wave and cannot see
+            # a Q80 block: the QKV GEMV + rope_kv pair runs instead (one more
+            # launch per layer for a single llama sequence)
+            self.fused_rope = False
         self._alloc_buffers()
 
     def _read_options(self):
@@ -266,7 +281,8 @@ class HipTransformer:
                   comm: Comm | None = None, n_batches: int = 32,
                   force_sync: bool = False,
                   n_slots: int = 1, kv_pages: int = 0,
-                  page_size: int = 64) -> "HipTransformer":
+                  page_size: int = 64,
+                  kv_dtype: str | None = None) -> "HipTransformer":
         from ..quants import Q40
         if m.header.weight_type != Q40:
             raise ValueError(
@@ -274,7 +290,7 @@ class HipTransformer:
                 "shipped format); f32/q80 .m files run on the CPU backend "
                 "(--gpu-index -1) or can be re-quantized with convert_hf.py")
         self = cls(config, device, comm, n_batches, force_sync, n_slots,
-                   kv_pages, page_size)
+                   kv_pages, page_size, kv_dtype)
         c, dev = config, self.device
         r, w = c.rank, c.world
 
@@ -326,11 +342,12 @@ class HipTransformer:
                   n_batches: int = 32, seed: int = 1234,
                   force_sync: bool = False,
                   n_slots: int = 1, kv_pages: int = 0,
-                  page_size: int = 64) -> "HipTransformer":
+                  page_size: int = 64,
+                  kv_dtype: str | None = None) -> "HipTransformer":
         """Random-init weights built directly on device (benches: no network
         for checkpoints, and an 8B .m file round-trip is pointless there)."""
         self = cls(config, device, comm, n_batches, force_sync, n_slots,
-                   kv_pages, page_size)
+                   kv_pages, page_size, kv_dtype)
         c, dev = config, self.device
         gen = torch.Generator(device=dev)
         gen.manual_seed(seed + c.rank)
@@ -458,7 +475,8 @@ class HipTransformer:
         self._build_bf16_shadow()
         cache = R.rope_cache(c.seq_len, c.head_dim, c.rope_theta, c.rope_scaling)
         self.rope_cache = cache.reshape(c.seq_len, c.head_dim).contiguous().to(dev)
-        kv_dt = torch.float32 if self.kv_f32 else torch.float16
+        kv_dt = (torch.int8 if self.kv_q80
+                 else torch.float32 if self.kv_f32 else torch.float16)
         kv_rows = self.n_slots * c.seq_len  # slot s = rows s*seq_len ...
         if self.page_map is not None:
             kv_rows = self.kv_pages * self.page_size
@@ -470,6 +488,28 @@ class HipTransformer:
                         for _ in range(c.n_layers)]
         self.v_cache = [torch.zeros(kv_rows, c.kv_dim0, dtype=kv_dt, device=dev)
                         for _ in range(c.n_layers)]
+        if self.kv_q80:
+            # the scale planes, indexed by the same cache row as the codes;
+            # zero codes and zero scales dequantise to 0 like an empty cache
+            def scales():
+                return [torch.zeros(kv_rows, c.kv_dim0 // QB,
+                                    dtype=torch.float16, device=dev)
+                        for _ in range(c.n_layers)]
+            self.k_scales, self.v_scales = scales(), scales()
+
+    def _kv_scales(self, l: int) -> dict:
+        """The keywords that hand layer l's scale planes to a positional
+        binding; none unless the cache is Q80."""
+        if not self.kv_q80:
+            return {}
+        return {"k_scales": self.k_scales[l], "v_scales": self.v_scales[l]}
+
+    def kv_cache_bytes(self) -> int:
+        """Bytes of all K/V planes of all layers (scale planes included)."""
+        planes = self.k_cache + self.v_cache
+        if self.kv_q80:
+            planes = planes + self.k_scales + self.v_scales
+        return sum(t.numel() * t.element_size() for t in planes)
 
     # ------------------------------------------------------------ stages
 
@@ -497,6 +537,7 @@ class HipTransformer:
     def _gemv_rope(self, l: int, lw: dict, NB: int, **deferred):
         """QKV GEMV with llama rope + KV write in its epilogue."""
         c = self.cfg
+        assert not self.kv_q80, "the rope epilogue has no Q80 cache form"
         self.k.q40_gemv_rope(lw["qkv"].qs, lw["qkv"].scales, *self.xq.triple(),
                              self.qkv_out, NB, self.rope_cache, self.pos,
                              self.k_cache[l], self.v_cache[l], c.q_dim0,
@@ -513,7 +554,7 @@ class HipTransformer:
                 self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0,
                 self.rope_cache, *addr.where, self.k_cache[l],
                 self.v_cache[l], c.head_dim, lw["q_norm"], lw["k_norm"],
-                c.norm_eps, B)
+                c.norm_eps, B, **self._kv_scales(l))
             return
         if c.is_qwen3:
             for col0, width, wn in ((0, c.q_dim0, lw["q_norm"]),
@@ -524,7 +565,7 @@ class HipTransformer:
         getattr(k, addr.rope_kv)(
             self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0, self.rope_cache,
             *addr.where, self.k_cache[l], self.v_cache[l], c.head_dim,
-            self.rope_style, B)
+            self.rope_style, B, **self._kv_scales(l))
 
     def _attn(self, l: int, B: int, addr: KVAddr, emit_q80: bool = True):
         """Attention of every row over its sequence's rows of layer l's
@@ -535,7 +576,8 @@ class HipTransformer:
             self.qkv_out, self.qkv_ld, self.k_cache[l], self.v_cache[l],
             self.zbuf[:B], *addr.where, B, c.n_heads0, self.kv_mul,
             c.head_dim, self.attn_splits, self.attn_ml, self.attn_o,
-            *addr.attn_scratch, *(self.zq.triple() if emit_q80 else ()))
+            *addr.attn_scratch, *(self.zq.triple() if emit_q80 else ()),
+            **self._kv_scales(l))
 
     def _swiglu_q80(self, out13, rows: int, qb: QuantBuf, *act):
         """act(w1 x) * (w3 x) over the fused W1|W3 output -> Q80 triple."""

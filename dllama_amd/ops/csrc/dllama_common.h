@@ -160,11 +160,28 @@ struct Q80Lane {
     float d;   // block scale
 };
 
-__device__ __forceinline__ Q80Lane q80_quant_group32(float v) {
-    const float amax = group32_reduce_max(fabsf(v));
+// the one quantiser: a value's code and scale, given its block's absmax
+__device__ __forceinline__ Q80Lane q80_quant_lane(float v, float amax) {
     const float d = amax / 127.0f;
     const float inv = d > 0.0f ? 1.0f / d : 0.0f;
     return {rintf(v * inv), d};
+}
+
+__device__ __forceinline__ Q80Lane q80_quant_group32(float v) {
+    return q80_quant_lane(v, group32_reduce_max(fabsf(v)));
+}
+
+// 16-lane sibling: lane j of a 16-lane group holds the interleaved pair
+// (2j, 2j+1) of the block (llama rope). Both codes share the block scale.
+struct Q80Pair {
+    float qf0, qf1;  // codes of elements 2j and 2j+1
+    float d;         // block scale
+};
+
+__device__ __forceinline__ Q80Pair q80_quant_group16x2(float v0, float v1) {
+    const float amax = group16_reduce_max(fmaxf(fabsf(v0), fabsf(v1)));
+    const Q80Lane c0 = q80_quant_lane(v0, amax);
+    return {c0.qf, q80_quant_lane(v1, amax).qf, c0.d};
 }
 
 // ---------------------------------------------------------------- Q80 wire
@@ -247,9 +264,12 @@ __device__ __forceinline__ float ssq_total_wave(const float *ssq, int b,
 }
 
 // KV-cache dtype helpers (f16 KV is the default; torch extensions build
-// with __HIP_NO_HALF_CONVERSIONS__, so conversions must be explicit)
+// with __HIP_NO_HALF_CONVERSIONS__, so conversions must be explicit). A Q80
+// cache (int8 code plane + f16 scale plane per K and V) is opt-in.
 __device__ __forceinline__ float kv_f(float v) { return v; }
 __device__ __forceinline__ float kv_f(__half v) { return __half2float(v); }
+// a Q80 cache code: the block scale is applied by the caller, once per run
+__device__ __forceinline__ float kv_f(int8_t v) { return (float)v; }
 template <typename T> __device__ __forceinline__ T kv_c(float v);
 template <> __device__ __forceinline__ float kv_c<float>(float v) { return v; }
 template <> __device__ __forceinline__ __half kv_c<__half>(float v) { return __float2half(v); }

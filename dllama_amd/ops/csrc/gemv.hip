@@ -964,6 +964,10 @@ void q40_gemv_rope(torch::Tensor qs, torch::Tensor scales, torch::Tensor xq,
                    c10::optional<torch::Tensor> ssq_in = c10::nullopt,
                    double eps = 0.0) {
     CHECK_CUDA(qs); CHECK_CONT(qs); CHECK_CONT(xq);
+    // the epilogue holds two rows per wave and cannot see a Q80 block
+    TORCH_CHECK(kc.scalar_type() != at::kChar && vc.scalar_type() != at::kChar,
+                "q40_gemv_rope has no Q80 KV cache form: run the QKV GEMV "
+                "and rope_kv(..., k_scales=, v_scales=)");
     GemvEpi e;
     e.cache = cache.data_ptr<float>();
     e.pos = pos.data_ptr<int>();

@@ -48,6 +48,22 @@ def q80_roundtrip(x: torch.Tensor) -> torch.Tensor:
     return q80_dequantize(q, s)
 
 
+def q80_quantize_f16(x: torch.Tensor):
+    """f32 [.., n] -> (codes int8 [.., n], scales f16 [.., n/32]): Q80 blocks
+    as they are stored (quants.quantize_q80, the Q80 KV cache). The codes
+    come from the f32 scale d = absmax/127; the stored scale is f16(d)."""
+    q, d, _ = q80_quantize(x)
+    return q, d.to(torch.float16)
+
+
+def q80_roundtrip_f16(x: torch.Tensor) -> torch.Tensor:
+    """Round trip through stored Q80 blocks: code * f32(f16(d)). Equals
+    quants.q80_roundtrip bit for bit; q80_roundtrip above keeps d in f32 (an
+    activation cast, whose scale never leaves registers)."""
+    q, s = q80_quantize_f16(x)
+    return q80_dequantize(q, s.float())
+
+
 # ------------------------------------------------------------ matmul
 
 def q40_planes_dequant(qs: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:

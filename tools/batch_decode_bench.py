@@ -17,7 +17,7 @@ contiguous in the pool. The single-sequence entry is left out then (a paged
 model steps rows only). --context N starts the timed decode at position N:
 the prompt is still --prefill tokens, the cache rows between hold zeros, and
 every step reads all N of them, so long contexts are timed without paying
-B long prefills.
+B long prefills. --kv-dtype q80 runs either form on the Q80 KV cache.
 
 Warmup and timing follow bench.py: untimed warmup steps on the shapes of
 the timed window, then a host clock around `--steps` steps ending in a
@@ -55,6 +55,8 @@ def main():
     ap.add_argument("--kv-pages", type=int, default=0,
                     help="page the KV cache: pool of this many pages")
     ap.add_argument("--page-size", type=int, default=64)
+    ap.add_argument("--kv-dtype", default=None, choices=["f16", "f32", "q80"],
+                    help="KV cache format (default: the model's, f16)")
     args = ap.parse_args()
     context = max(args.context, args.prefill)
     if not torch.cuda.is_available():
@@ -74,7 +76,9 @@ def main():
     t0 = time.time()
     paging = (dict(kv_pages=args.kv_pages, page_size=args.page_size)
               if args.kv_pages else {})
-    model = HipTransformer.synthetic(cfg, device=device, n_slots=max(batches),
+    if args.kv_dtype is not None:
+        paging["kv_dtype"] = args.kv_dtype
+    model =HipTransformer.synthetic(cfg, device=device, n_slots=max(batches),
                                      **paging)
     model.device_sampling = True
     torch.cuda.synchronize(device)
@@ -165,6 +169,8 @@ def main():
                    "kv_pages": args.kv_pages,
                    "page_size": args.page_size if args.kv_pages else None,
                    "n_slots": model.n_slots,
+                   "kv_dtype": model.kv_dtype,
+                   "kv_cache_bytes": model.kv_cache_bytes(),
                    "sampling": "on device, temperature 0",
                    "data": "synthetic (random-init weights, random prompt)"},
     }))

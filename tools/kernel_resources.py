@@ -20,7 +20,13 @@ SeqRows>`: 2 q loads, then inside the loop 4 `global_load_dwordx4` (K) and
 16 `global_load_dword` (V) with no `s_waitcnt vmcnt` between them, then
 `; sched_barrier`, then the first wait, `s_waitcnt vmcnt(19)`. A
 `vmcnt(0)` between the loads, or V loads below the barrier, is the serial
-form that profiles/r07_wide_attention.md describes (4.4 -> 14 us).
+form that profiles/r07_wide_attention.md describes (4.4 -> 14 us). The Q80
+forms, `k_attn_wide<V, signed char, Q80Rows<..>>`, issue 40 loads per round
+the same way (4 K runs, 4 K scales, 16 V dwords, 16 V scale dwords, all but
+the K runs `global_load_dword`), then `; sched_barrier`, then the first
+wait, `vmcnt(39)`; a `flat_load`, a `global_load_ushort` / `_ubyte` or a
+wait between those loads is the serial form again
+(profiles/r09_q80_kv.md).
 
 Second manual check: `k_q40_gemv<1, 2, 5, 0>` (the hand-off form of
 q40_gemv_resid_q) exchanges rows between workgroups of one launch. Expected
