@@ -416,9 +416,15 @@ __global__ void k_q40_gemv_grouped(const uint8_t *__restrict__ qs,
     const int wpb = blockDim.x / WAVE;
     const int full_lane = threadIdx.x % WAVE;
     const int grp = full_lane / LPP;
-    const int row0 = ((blockIdx.x * wpb + threadIdx.x / WAVE) * NGRP + grp) * 2;
+    const int wave_row0 = (blockIdx.x * wpb + threadIdx.x / WAVE) * NGRP * 2;
     const int slot = blockIdx.y;
-    if (row0 >= d) return;
+    if (wave_row0 >= d) return;  // wave-uniform
+    // A group past the last row keeps its lanes and streams row 0 unstored:
+    // the gate and the ssq total below shuffle across the whole wave, and a
+    // shuffle reads 0 from a lane that has exited (with LPP < 64 and d not
+    // a multiple of the wave's rows that lost experts and ssq slots).
+    const bool valid = wave_row0 + grp * 2 < d;
+    const int row0 = valid ? wave_row0 + grp * 2 : 0;
     const int lane = full_lane % LPP;
     const int nb = n / QB;
     const int nbp = nb >> 1;
@@ -484,7 +490,7 @@ __global__ void k_q40_gemv_grouped(const uint8_t *__restrict__ qs,
         acc0 *= inv;
         acc1 *= inv;
     }
-    if (lane == 0) {
+    if (lane == 0 && valid) {
         y[(int64_t)slot * d + row0] = acc0;
         if (row0 + 1 < d) y[(int64_t)slot * d + row0 + 1] = acc1;
     }

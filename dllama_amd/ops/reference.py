@@ -92,6 +92,107 @@ def q40_matmul(x: torch.Tensor, w_f32: torch.Tensor,
     return x @ w_f32.t()
 
 
+# ------------------------------------------------------------ exact oracle
+
+def q40_unpack(qs: torch.Tensor) -> torch.Tensor:
+    """Device-layout nibble plane uint8 [.., d, n/2] -> int64 [.., d, nb, 32]
+    in -8..7: in block byte j the low nibble is element j, the high nibble
+    element j+16."""
+    half = qs.shape[-1]
+    b = qs.cpu().reshape(*qs.shape[:-1], half // 16, 16).to(torch.int64)
+    return torch.cat([(b & 0xF) - 8, (b >> 4) - 8], dim=-1)
+
+
+def q40_q80_exact(qs, scales, xq, xs, blocks=None):
+    """Exact Q40 x Q80 product: (y, A) float64 [B, d].
+
+    qs uint8 [d, n/2] and scales f16/f32 [d, n/32] are the device-layout
+    weight planes, xq int8 [B, n] and xs f32 [B, n/32] the Q80 codes and
+    scales. Per block the integer dot is taken in int64, then
+        t[b,row,j] = float64(scales[row,j]) * float64(xs[b,j]) * idot[b,row,j]
+        y = sum_j t        A = sum_j |t|
+    blocks=(j0, j1) restricts both sums to that block range (a K-split
+    slice). The blocksum is not an input: the true value of the kernels'
+    `idot_unsigned - 8*bsum` is the signed dot, so a wrong blocksum shows as
+    an error of y. float64 holds every t exactly up to 2^-53, so y is good to
+    about nb * 2^-53 * A."""
+    w = q40_unpack(qs)                                   # [d, nb, 32]
+    d, nb, _ = w.shape
+    xq = xq.cpu()
+    B = xq.shape[0]
+    x = xq.reshape(B, nb, Q_BLOCK).to(torch.int64)
+    j0, j1 = (0, nb) if blocks is None else blocks
+    idot = torch.einsum("rjk,bjk->brj", w[:, j0:j1], x[:, j0:j1])
+    sw = scales.cpu().to(torch.float64)[:, j0:j1]
+    sx = xs.cpu().to(torch.float64)[:, j0:j1]
+    t = sw.unsqueeze(0) * sx.unsqueeze(1) * idot.to(torch.float64)
+    return t.sum(-1), t.abs().sum(-1)
+
+
+def q40_q80_bound(nb: int, A):
+    """Largest |f32 kernel output - q40_q80_exact y| of a correct kernel:
+    (nb + 2) * 2^-24 * A, with u = 2^-24 the f32 unit roundoff.
+
+    - The integer part is exact in f32. A kernel forms either the signed
+      block dot (MFMA GEMM) or (float)idot_unsigned - 8*bsum (dot4 GEMV);
+      |idot_unsigned| <= 32*15*127 = 60960 and |8*bsum| <= 8*32*127 = 32512,
+      so both operands and their difference are integers below 2^24.
+    - sw*sx rounds once: the kernel's term is t_j(1+e_j), |e_j| <= u.
+    - Summing nb such terms in f32 in ANY order (fma or mul+add chain, lane
+      partition, wave tree reduce, K-split partials and their reduction)
+      errs by at most gamma_{nb-1} * sum|t_j(1+e_j)| with
+      gamma_k = k*u/(1 - k*u); an fma folds the product's rounding into the
+      add's, so it never does worse than this. Adding the zeros of idle
+      lanes is exact.
+    - Together: u*A + gamma_{nb-1}*(1+u)*A <= (nb + 2)*u*A for nb*u << 1
+      (the margin of 2u*A absorbs the second-order terms up to nb ~ 2^23).
+    A is the oracle's sum_j |t_j|. Derived, not tuned: a correct kernel over
+    it means this derivation is wrong."""
+    return (nb + 2) * 2.0 ** -24 * A
+
+
+def q80_emit_check(codes, scales, bsum, v, v_tol, scale_rtol=0.0):
+    """Assert that (codes int8 [.., n], scales [.., n/32], bsum [.., n/32])
+    is a Q80 triple of values whose float64 truth is v [.., n] and that the
+    emitting kernel saw with an error of at most v_tol (scalar or [.., n]).
+
+    From q80_quant_lane (d = amax/127, code = rintf(x * (1/d))), per block:
+      |code| <= 127
+      bsum == sum(codes)                      exactly
+      |d - max|v|/127| <= max(v_tol)/127 + 2^-22 * d
+      |code*d - v| <= d/2 + v_tol + 127 * 2^-22 * d
+    The kernel's amax is within max(v_tol) of max|v| and the divide rounds
+    once (u*d). x*(1/d) carries the reciprocal's and the product's rounding,
+    2u relative on a quotient of at most 127; rintf then adds at most 1/2,
+    so |code - x/d| <= 1/2 + 127*2u. 2^-22 = 4u leaves room for divides
+    that are good to 2 ulp instead of correctly rounded.
+
+    The TP wire format stores f16(d) and no blocksum: pass bsum=None and
+    scale_rtol=2^-11 (f16 half-ulp); the scale is then known to that
+    relative error only, which adds scale_rtol*d to the scale check and
+    127*scale_rtol*d to the code check."""
+    codes = codes.cpu()
+    n = codes.shape[-1]
+    lead = codes.shape[:-1]
+    c = codes.reshape(*lead, n // Q_BLOCK, Q_BLOCK).to(torch.float64)
+    d = scales.cpu().to(torch.float64).reshape(*lead, n // Q_BLOCK)
+    v = torch.as_tensor(v, dtype=torch.float64).reshape(c.shape)
+    tol = torch.as_tensor(v_tol, dtype=torch.float64)
+    tol = tol.expand(*lead, n).reshape(c.shape) if tol.dim() else tol.expand(c.shape)
+    assert c.abs().max() <= 127, ("code out of range", c.abs().max().item())
+    if bsum is not None:
+        bs = bsum.cpu().to(torch.float64).reshape(*lead, n // Q_BLOCK)
+        assert torch.equal(bs, c.sum(-1)), \
+            ("blocksum != sum(codes)", (bs - c.sum(-1)).abs().max().item())
+    eps4 = 2.0 ** -22 + scale_rtol
+    d_err = (d - v.abs().amax(-1) / 127.0).abs()
+    d_tol = tol.amax(-1) / 127.0 + eps4 * d
+    assert (d_err <= d_tol).all(), ("scale", (d_err - d_tol).max().item())
+    c_err = (c * d.unsqueeze(-1) - v).abs()
+    c_tol = (d / 2 + 127 * eps4 * d).unsqueeze(-1) + tol
+    assert (c_err <= c_tol).all(), ("code", (c_err - c_tol).max().item())
+
+
 # ------------------------------------------------------------ norm / act
 
 def rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:

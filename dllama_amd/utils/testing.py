@@ -7,6 +7,55 @@ from .. import tokenizer as tok
 from .. import model_file as mf
 
 
+def natural_q40_planes(d: int, n: int, seed: int):
+    """Gaussian weights (std 0.1) through quants.quantize_q40 -> device-layout
+    planes (qs uint8 [d, n/2], scales f16 [d, n/32]) as CPU tensors."""
+    import numpy as np
+    import torch
+    from .. import quants
+    rng = np.random.default_rng(seed)
+    w = rng.standard_normal((d, n)).astype(np.float32) * 0.1
+    qs, sc = quants.q40_to_planes(quants.quantize_q40(w), d, n)
+    return torch.from_numpy(qs), torch.from_numpy(sc)
+
+
+def adversarial_q40_q80(d: int, n: int, rows: int, seed: int):
+    """Hand-built Q40 planes and Q80 triple at the corners the quantisers
+    rarely reach; no kernel in the loop. CPU tensors
+    (qs, scales, xq, xs, xbs):
+      qs      uniform random bytes, one weight row all 0x00 (every nibble
+              -8) and one all 0xFF (every nibble +7)
+      scales  f16, random sign, magnitude 2^U[-10,-3]
+      xq      codes uniform in [-127, 127] (-128 never: the quantiser cannot
+              emit it); per input row one block all +127, one all -127 and
+              one all zero whose scale is 0, where the row has that many
+      xs      uniform in [2^-8, 2^-2]
+      xbs     the exact code sum"""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(seed)
+    nb = n // 32
+    qs = rng.integers(0, 256, (d, n // 2), dtype=np.uint8)
+    r0 = int(rng.integers(0, d))
+    qs[r0] = 0x00
+    if d > 1:
+        qs[(r0 + 1 + int(rng.integers(0, d - 1))) % d] = 0xFF
+    mag = np.exp2(rng.uniform(-10.0, -3.0, (d, nb)))
+    sc = (mag * rng.choice([-1.0, 1.0], (d, nb))).astype(np.float16)
+    xq = rng.integers(-127, 128, (rows, nb, 32)).astype(np.int8)
+    xs = rng.uniform(2.0 ** -8, 2.0 ** -2, (rows, nb)).astype(np.float32)
+    for r in range(rows):
+        special = rng.permutation(nb)[:3]
+        for j, fill in zip(special, (127, -127, 0)):
+            xq[r, j] = fill
+            if fill == 0:
+                xs[r, j] = 0.0
+    xbs = xq.astype(np.int32).sum(-1).astype(np.float32)
+    return (torch.from_numpy(qs), torch.from_numpy(sc),
+            torch.from_numpy(xq.reshape(rows, n)), torch.from_numpy(xs),
+            torch.from_numpy(xbs))
+
+
 def make_byte_tokenizer(path: str, chat_template: str | None = None) -> None:
     """A byte-level BPE tokenizer: 256 byte tokens, a few merges, and
     llama3-style special tokens. Good enough to exercise the full
