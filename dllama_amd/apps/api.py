@@ -15,6 +15,10 @@ Behavior parity with the reference API server (src/dllama-api.cpp):
     there (no NaiveCache reuse across slots) unless --kv-pages M pages the
     KV cache: then whole pages of a shared prompt prefix or chat history
     are reused across slots (usage.prompt_tokens_details.cached_tokens).
+  - logprobs / top_logprobs (beyond the reference): per generated token its
+    log-probability and the top_logprobs most likely tokens, under the
+    model's distribution at temperature 1 ("raw logprobs"). Not under
+    tensor parallelism; no prompt-token logprobs (echo).
 """
 
 from __future__ import annotations
@@ -31,7 +35,7 @@ from ..engine import BatchEngine
 from ..tokenizer import Sampler
 
 from ..tokenizer import (ChatItem, ChatTemplateGenerator, EosDetector,
-                         TEMPLATE_UNKNOWN, chat_stops)
+                         EOS, MAYBE_EOS, TEMPLATE_UNKNOWN, chat_stops)
 from .main import build_parser, load_engine
 
 
@@ -57,6 +61,98 @@ class NaiveCache:
         self.tokens = list(tokens)
 
 
+class BadRequest(ValueError):
+    """A request the server answers with a 400; `param` names the field."""
+
+    def __init__(self, message: str, param: str | None = None):
+        super().__init__(message)
+        self.param = param
+
+
+def logprobs_requested(body: dict, world: int = 1) -> int | None:
+    """K of a request's logprobs / top_logprobs fields (None: not asked
+    for); BadRequest for what the API refuses."""
+    want, top = body.get("logprobs"), body.get("top_logprobs")
+    if want is not None and not isinstance(want, bool):
+        raise BadRequest("logprobs must be a boolean", "logprobs")
+    if top is not None:
+        if isinstance(top, bool) or not isinstance(top, int) or not 0 <= top <= 20:
+            raise BadRequest("top_logprobs must be an integer between 0 and 20",
+                             "top_logprobs")
+        if not want:
+            raise BadRequest("top_logprobs requires logprobs to be true",
+                             "top_logprobs")
+    if not want:
+        return None
+    if world > 1:
+        raise BadRequest("logprobs is not supported under tensor parallelism",
+                         "logprobs")
+    return top or 0
+
+
+class _Deltas:
+    """One request's way from tokens to text deltas: the streaming decoder
+    feeds the EosDetector, and what it releases goes to emit(delta). With
+    logprobs, emit(delta, entries) also gets the entries of the tokens whose
+    text that delta released: tokens the detector held back go with the
+    delta that releases them, and the token that ended the generation (an
+    EOS id, or the one that completed a stop string) is not listed."""
+
+    def __init__(self, tok, detector, emit, logprobs: bool):
+        self.tok, self.detector, self.emit = tok, detector, emit
+        self.logprobs = logprobs
+        self.text: list[str] = []
+        self.pending: list[dict] = []
+        self.kind = None
+
+    def on_token(self, t):
+        # streaming-decoder first: UTF-8-safe pieces into the detector
+        self.kind = self.detector.append(t, self.tok.decode(t))
+        if not self.logprobs:
+            self._release()
+
+    def on_logprobs(self, entry):  # called right after on_token
+        if self.kind != EOS:
+            self.pending.append(self._json(entry))
+        self._release()
+
+    def _release(self):
+        if self.kind == MAYBE_EOS:
+            return
+        delta = self.detector.get_delta()
+        if delta:
+            self.text.append(delta)
+            self._emit(delta)
+            self.detector.reset()
+        elif self.pending:
+            self._emit("")
+
+    def finish(self):
+        """Entries still held when the generation ended (max_tokens with a
+        possible stop string pending): their text is never released."""
+        if self.pending:
+            self._emit("")
+
+    def _emit(self, delta):
+        if self.logprobs:
+            entries, self.pending = self.pending, []
+            self.emit(delta, entries)
+        else:
+            self.emit(delta)
+
+    def _piece(self, token: int, logprob: float) -> dict:
+        raw = self.tok.vocab[token] if 0 <= token < len(self.tok.vocab) else b""
+        return {"token": raw.decode("utf-8", errors="replace"),
+                # JSON has no infinity
+                "logprob": logprob if logprob > -9999.0 else -9999.0,
+                "bytes": list(raw)}
+
+    def _json(self, entry) -> dict:
+        out = self._piece(entry.token, entry.logprob)
+        out["top_logprobs"] = [self._piece(i, lp) for i, lp in entry.top]
+        return out
+
+
 class BatchScheduler:
     """The one thread that owns the model in multi-slot serving. Handlers
     hand it requests over a queue; it admits them into a BatchEngine between
@@ -71,12 +167,12 @@ class BatchScheduler:
         self.thread.start()
 
     def submit(self, tokens, max_tokens, sampler, on_token, stop_check, on_done,
-               stats_out=None):
+               stats_out=None, logprobs=None, on_logprobs=None):
         """on_done(error_or_None) is called once, after the last on_token.
         stats_out: a list that receives the sequence's GenStats when it is
         queued in the engine."""
         self.inbox.put((tokens, max_tokens, sampler, on_token, stop_check,
-                        on_done, stats_out))
+                        logprobs, on_logprobs, on_done, stats_out))
 
     def stop(self):
         self.inbox.put(None)
@@ -144,14 +240,16 @@ class ApiState:
         self.default_topp = args.topp
         self.default_seed = args.seed if args.seed is not None else int(time.time())
 
-    def complete(self, body: dict, emit):
-        """Run one chat completion; emit(delta_text) streams chunks."""
+    def complete(self, body: dict, emit, logprobs: int | None = None):
+        """Run one chat completion; emit(delta_text) streams chunks. With
+        logprobs = K (logprobs_requested) it is emit(delta_text, entries):
+        the API's logprobs content of the tokens that delta released."""
         items = [ChatItem(m.get("role", "user"), m.get("content", ""))
                  for m in body.get("messages", [])]
         text = self.template.generate(items, True).content
         tokens = self.tok.encode(text)
         if self.scheduler is not None:
-            return self._complete_batched(body, tokens, emit)
+            return self._complete_batched(body, tokens, emit, logprobs)
         start = self.cache.resolve(tokens)
         self.engine.reset(start)
         max_tokens = int(body.get("max_tokens") or 256)
@@ -172,22 +270,15 @@ class ApiState:
         stops = chat_stops(self.tok) + user_stop
         detector = EosDetector(self.tok.eos_token_ids, stops)
         self.tok.reset_decoder()
-        out_text = []
-
-        def on_token(t):
-            # streaming-decoder first: UTF-8-safe pieces into the detector
-            piece = self.tok.decode(t)
-            kind = detector.append(t, piece)
-            if kind != 0:  # not MAYBE_EOS
-                delta = detector.get_delta()
-                if delta:
-                    out_text.append(delta)
-                    emit(delta)
-                    detector.reset()
-
+        deltas = _Deltas(self.tok, detector, emit, logprobs is not None)
+        out_text = deltas.text
+        more = ({} if logprobs is None else
+                {"logprobs": logprobs, "on_logprobs": deltas.on_logprobs})
         gen_tokens, _ = self.engine.generate(
-            tokens[start:], max_tokens, on_token=on_token,
-            stop_check=lambda t: detector.is_eos(t) or detector.eos_pos >= 0)
+            tokens[start:], max_tokens, on_token=deltas.on_token,
+            stop_check=lambda t: detector.is_eos(t) or detector.eos_pos >= 0,
+            **more)
+        deltas.finish()
         # cache only EVALUATED tokens: the last sampled token was never fed
         # through the model, so its KV row does not exist (reference caches
         # the evaluated endPos, dllama-api.cpp:470-473)
@@ -195,7 +286,8 @@ class ApiState:
         return "".join(out_text), len(tokens), len(gen_tokens)
 
 
-    def _complete_batched(self, body: dict, tokens: list, emit):
+    def _complete_batched(self, body: dict, tokens: list, emit,
+                          logprobs: int | None = None):
         """complete() in multi-slot mode: the request gets its own sampler,
         detector and streaming decoder, runs on the scheduler thread next to
         the other requests, and its deltas come back over a queue."""
@@ -214,22 +306,25 @@ class ApiState:
         tok = self.tok.fork_decoder()
         deltas: queue.Queue = queue.Queue()
         generated = [0]
+        # runs on the scheduler thread: what it releases crosses the queue
+        stream = _Deltas(tok, detector, lambda *released: deltas.put(released),
+                         logprobs is not None)
 
         def on_token(t):
             generated[0] += 1
-            kind = detector.append(t, tok.decode(t))
-            if kind != 0:  # not MAYBE_EOS
-                delta = detector.get_delta()
-                if delta:
-                    deltas.put(delta)
-                    detector.reset()
+            stream.on_token(t)
+
+        def on_done(error):
+            if error is None:
+                stream.finish()
+            deltas.put(error if error is not None else StopIteration)
 
         stats = []
         self.scheduler.submit(
             tokens, int(body.get("max_tokens") or 256), sampler, on_token,
             lambda t: detector.is_eos(t) or detector.eos_pos >= 0,
-            lambda error: deltas.put(error if error is not None else StopIteration),
-            stats)
+            on_done, stats, logprobs,
+            stream.on_logprobs if logprobs is not None else None)
         out_text = []
         while True:
             item = deltas.get()
@@ -237,8 +332,8 @@ class ApiState:
                 break
             if isinstance(item, Exception):
                 raise item
-            out_text.append(item)
-            emit(item)
+            out_text.append(item[0])
+            emit(*item)
         # a fourth value on this path only: the prompt tokens that came from
         # shared KV pages (0 on an unpaged model)
         return ("".join(out_text), len(tokens), generated[0],
@@ -282,6 +377,13 @@ class Handler(BaseHTTPRequestHandler):
         except json.JSONDecodeError:
             self._json(400, {"error": "invalid json"})
             return
+        try:
+            logprobs = logprobs_requested(body, STATE.comm.world)
+        except BadRequest as e:
+            self._json(400, {"error": {
+                "message": str(e), "type": "invalid_request_error",
+                "param": e.param, "code": None}})
+            return
         rid = f"chatcmpl-{uuid.uuid4().hex[:12]}"
         created = int(time.time())
         stream = bool(body.get("stream"))
@@ -292,15 +394,18 @@ class Handler(BaseHTTPRequestHandler):
             self.send_header("Transfer-Encoding", "chunked")
             self.end_headers()
 
-            def emit(delta):
+            def emit(delta, entries=None):
+                choice = {"index": 0, "delta": {"content": delta},
+                          "finish_reason": None}
+                if entries is not None:
+                    choice["logprobs"] = {"content": entries}
                 chunk = {"id": rid, "object": "chat.completion.chunk",
                          "created": created, "model": STATE.model_name,
-                         "choices": [{"index": 0, "delta": {"content": delta},
-                                      "finish_reason": None}]}
+                         "choices": [choice]}
                 self._chunk(f"data: {json.dumps(chunk)}\n\n")
 
             try:
-                STATE.complete(body, emit)
+                STATE.complete(body, emit, logprobs)
             finally:
                 fin = {"id": rid, "object": "chat.completion.chunk",
                        "created": created, "model": STATE.model_name,
@@ -310,9 +415,11 @@ class Handler(BaseHTTPRequestHandler):
                 self._chunk("data: [DONE]\n\n")
                 self.wfile.write(b"0\r\n\r\n")
         else:
+            content = []
             try:
                 text, n_prompt, n_gen, *cached = STATE.complete(
-                    body, lambda d: None)
+                    body, lambda d, entries=(): content.extend(entries),
+                    logprobs)
             except Exception as e:  # noqa: BLE001
                 self._json(500, {"error": {"message": str(e), "type": "server_error"}})
                 return
@@ -320,12 +427,15 @@ class Handler(BaseHTTPRequestHandler):
                      "total_tokens": n_prompt + n_gen}
             if cached:  # the batched path
                 usage["prompt_tokens_details"] = {"cached_tokens": cached[0]}
+            choice = {"index": 0, "message":
+                      {"role": "assistant", "content": text},
+                      "finish_reason": "stop"}
+            if logprobs is not None:
+                choice["logprobs"] = {"content": content}
             self._json(200, {
                 "id": rid, "object": "chat.completion", "created": created,
                 "model": STATE.model_name,
-                "choices": [{"index": 0, "message":
-                             {"role": "assistant", "content": text},
-                             "finish_reason": "stop"}],
+                "choices": [choice],
                 "usage": usage})
 
     def _chunk(self, s: str):

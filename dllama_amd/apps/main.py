@@ -387,6 +387,17 @@ def run_perplexity(args) -> int:
         t = torch.tensor(chunk, dtype=torch.int64)
         p = torch.arange(pos, pos + len(chunk), dtype=torch.int64)
         logits = engine.model.forward(t, p)  # [B, vocab]
+        if hasattr(engine.model, "logprob_targets"):
+            # HIP backend: the block stays on the GPU; one float per row
+            # comes back (-1: the last row has no next token)
+            nxt = [tokens[i + j + 1] if i + j + 1 < len(tokens) else -1
+                   for j in range(len(chunk))]
+            for t_next, lp in zip(nxt, engine.model.logprob_targets(logits, nxt)):
+                if t_next >= 0:
+                    nll -= lp
+                    count += 1
+            pos += len(chunk)
+            continue
         logits = logits.detach().float().cpu()
         for j in range(len(chunk)):
             nxt_idx = i + j + 1

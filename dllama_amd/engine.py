@@ -18,11 +18,40 @@ at a time; InferenceEngine stays the single-sequence path.
 from __future__ import annotations
 
 import time
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import torch
 
+from .ops.reference import logprob_rows_ref
 from .tokenizer import Sampler
+
+
+@dataclass
+class TokenLogprob:
+    """A generated token's log-probability under the model's distribution at
+    temperature 1 (before top-p, whatever the request samples with), and the
+    most likely tokens at that step as (id, logprob), most likely first."""
+    token: int
+    logprob: float
+    top: list = field(default_factory=list)
+
+
+def _entry_from_logits(row: torch.Tensor, token: int, k: int) -> TokenLogprob:
+    """The host path: the oracle on the logits row the sampler saw."""
+    _, lp, top_lp, top_id = logprob_rows_ref(row.reshape(1, -1), [token], k)
+    return TokenLogprob(token, float(lp[0]), list(zip(
+        top_id[0, :k].tolist(), top_lp[0, :k].tolist())))
+
+
+def _entry_from_device(result, token: int, sampled, row, k: int) -> TokenLogprob:
+    """From the device's (lse, logprob, top_ids, top_logprobs) of a row.
+    sampled None: the device sampler gave up and `token` was resampled on
+    the host from `row`; its log-probability is logit - lse."""
+    lse, lp, ids, lps = result
+    if sampled is None:
+        lp = float(row[token]) - lse
+    return TokenLogprob(token, lp, [(i, v) for i, v in zip(ids[:k], lps[:k])
+                                    if i >= 0])
 
 
 @dataclass
@@ -34,6 +63,8 @@ class GenStats:
     # prompt tokens whose K/V came from shared prefix pages (BatchEngine on
     # a paged model); they were not stepped
     cached_tokens: int = 0
+    # one TokenLogprob per generated token when the request asked for them
+    logprobs: list | None = None
 
     @property
     def eval_tok_s(self) -> float:
@@ -105,24 +136,51 @@ class InferenceEngine:
         temperature 0 — the same stream as Sampler.sample."""
         return sampler.next_coin() if sampler.temperature != 0.0 else 0.0
 
-    def decode_sample(self, token: int, sampler: Sampler) -> int:
+    def decode_sample(self, token: int, sampler: Sampler,
+                      logprobs: int | None = None):
         """One decode step with the token sampled on device. When the device
         sampler gives up (more candidates than its cap) the logits it left in
-        place are resampled on the host path with the same coin."""
+        place are resampled on the host path with the same coin. With
+        logprobs (the model's set_logprobs is on) returns (token, entry)."""
         t = torch.tensor([token], dtype=torch.int64)
         p = torch.tensor([self.pos], dtype=torch.int64)
         coin = self._coin(sampler)
-        nxt = self.model.forward_sample(t, p, coin, sampler.temperature,
-                                        sampler.topp)
+        nxt = sampled = self.model.forward_sample(t, p, coin, sampler.temperature,
+                                                  sampler.topp)
         self.pos += 1
         if nxt is None:
             nxt = sampler.sample_with_coin(self.model.last_logits(), coin)
-        return nxt
+        if logprobs is None:
+            return nxt
+        return nxt, _entry_from_device(self.model.last_logprobs(), nxt, sampled,
+                                       self.model.last_logits(), logprobs)
 
     def generate(self, prompt_tokens: list[int], max_tokens: int,
-                 on_token=None, stop_check=None) -> tuple[list[int], GenStats]:
+                 on_token=None, stop_check=None, logprobs: int | None = None,
+                 on_logprobs=None) -> tuple[list[int], GenStats]:
         """Greedy/sampled generation. on_token(token_id) is called per new
-        token; stop_check(token_id) -> bool ends generation."""
+        token; stop_check(token_id) -> bool ends generation. logprobs = K
+        (0..20): stats.logprobs gets one TokenLogprob per generated token
+        with its K most likely alternatives, and on_logprobs(entry) is called
+        right after on_token. The tokens do not depend on it."""
+        if logprobs is None:
+            return self._generate(prompt_tokens, max_tokens, on_token,
+                                  stop_check, None, None)
+        if not 0 <= logprobs <= 20:
+            raise ValueError(f"logprobs must be 0..20 (got {logprobs})")
+        switch = (self._device_sampling()
+                  and hasattr(self.model, "set_logprobs"))
+        if switch:
+            self.model.set_logprobs(True)
+        try:
+            return self._generate(prompt_tokens, max_tokens, on_token,
+                                  stop_check, logprobs, on_logprobs)
+        finally:
+            if switch:
+                self.model.set_logprobs(False)
+
+    def _generate(self, prompt_tokens, max_tokens, on_token, stop_check,
+                  logprobs, on_logprobs):
         stats = GenStats()
         assert len(prompt_tokens) >= 1
 
@@ -136,32 +194,55 @@ class InferenceEngine:
         out: list[int] = []
         sampler = self.sampler or Sampler(logits.shape[-1], 0.0, 0.9, 12345)
         on_device = self._device_sampling()
+        lp_device = on_device and hasattr(self.model, "set_logprobs")
+        if logprobs is not None:
+            stats.logprobs = []
+
+        def emit(token, entry):
+            out.append(token)
+            if on_token:
+                on_token(token)
+            if logprobs is not None:
+                stats.logprobs.append(entry)
+                if on_logprobs:
+                    on_logprobs(entry)
+
         t0 = time.perf_counter()
+        entry = None
         if on_device:
             coin = self._coin(sampler)
-            token = self.model.sample_row(logits, coin, sampler.temperature,
-                                          sampler.topp)
+            token = sampled = self.model.sample_row(
+                logits, coin, sampler.temperature, sampler.topp)
             if token is None:
                 token = sampler.sample_with_coin(logits, coin)
+            if logprobs is not None and lp_device:
+                entry = _entry_from_device(self.model.last_logprobs(), token,
+                                           sampled, logits, logprobs)
         else:
             token = sampler.sample(logits)
-        out.append(token)
-        if on_token:
-            on_token(token)
+        if logprobs is not None and entry is None:
+            entry = _entry_from_logits(logits, token, logprobs)
+        emit(token, entry)
         seq_len = getattr(getattr(self.model, "cfg", None), "seq_len", None)
         for _ in range(max_tokens - 1):
             if stop_check and stop_check(token):
                 break
             if seq_len is not None and self.pos >= seq_len:
                 break  # context window exhausted (reference clamps via seqLen)
-            if on_device:
+            entry = None
+            if on_device and logprobs is not None and lp_device:
+                token, entry = self.decode_sample(token, sampler, logprobs)
+            elif on_device:
                 token = self.decode_sample(token, sampler)
+                if logprobs is not None:
+                    entry = _entry_from_logits(self.model.last_logits(), token,
+                                               logprobs)
             else:
                 logits = self.decode_one(token)
                 token = sampler.sample(logits)
-            out.append(token)
-            if on_token:
-                on_token(token)
+                if logprobs is not None:
+                    entry = _entry_from_logits(logits, token, logprobs)
+            emit(token, entry)
         self._sync_device()
         stats.decode_time = time.perf_counter() - t0
         stats.decode_tokens = len(out)
@@ -171,7 +252,10 @@ class InferenceEngine:
 class _Sequence:
     """One submitted request of a BatchEngine."""
 
-    def __init__(self, prompt, max_tokens, sampler, on_token, stop_check):
+    def __init__(self, prompt, max_tokens, sampler, on_token, stop_check,
+                 logprobs=None, on_logprobs=None):
+        self.logprobs = logprobs
+        self.on_logprobs = on_logprobs
         self.prompt = list(prompt)
         self.max_tokens = max_tokens
         self.sampler = sampler
@@ -184,7 +268,8 @@ class _Sequence:
         self.written = 0      # positions whose K/V the slot holds
         self.out: list[int] = []
         self.done = False
-        self.stats = GenStats(prefill_tokens=len(self.prompt))
+        self.stats = GenStats(prefill_tokens=len(self.prompt),
+                              logprobs=None if logprobs is None else [])
         self._t0 = None       # when first scheduled, then when first sampled
 
     @property
@@ -252,10 +337,15 @@ class BatchEngine:
 
     def submit(self, prompt_tokens: list[int], max_tokens: int,
                sampler: Sampler | None = None, on_token=None,
-               stop_check=None) -> _Sequence:
+               stop_check=None, logprobs: int | None = None,
+               on_logprobs=None) -> _Sequence:
         """Queue a request; the handle's .tokens grows as it generates and
         .done turns True when it ended (max_tokens, stop_check or the end
-        of the context window), .stats holding its timing."""
+        of the context window), .stats holding its timing. logprobs = K
+        (0..20): .stats.logprobs gets one TokenLogprob per generated token
+        and on_logprobs(entry) is called right after on_token."""
+        if logprobs is not None and not 0 <= logprobs <= 20:
+            raise ValueError(f"logprobs must be 0..20 (got {logprobs})")
         if len(prompt_tokens) < 1:
             raise ValueError("empty prompt")
         if len(prompt_tokens) > self.seq_len:
@@ -272,7 +362,7 @@ class BatchEngine:
         if sampler is None:
             sampler = Sampler(self.model.cfg.vocab_size, 0.0, 0.9, 12345)
         seq = _Sequence(prompt_tokens, max_tokens, sampler, on_token,
-                        stop_check)
+                        stop_check, logprobs, on_logprobs)
         self.waiting.append(seq)
         return seq
 
@@ -354,6 +444,13 @@ class BatchEngine:
         slots = [seq.slot for seq, _, _, _ in rows]
         positions = [pos for _, _, pos, _ in rows]
         model = self.model
+        # the model computes log-probabilities while any running sequence
+        # asks for them, and only the asking rows are turned into entries
+        asking = any(seq.logprobs is not None for seq in self.running)
+        lp_device = self._on_device() and hasattr(model, "set_logprobs")
+        if lp_device:
+            model.set_logprobs(asking)
+        entries = [None] * len(rows)
         if self._on_device():
             coins = [self._coin(seq.sampler) if smp else 0.0
                      for seq, _, _, smp in rows]
@@ -363,15 +460,36 @@ class BatchEngine:
             picked = model.forward_rows_sample(tokens, slots, positions, coins,
                                                temps, topps)
             logits = None
+            sampled = list(picked)
             for b, (seq, _, _, smp) in enumerate(rows):
                 if smp and picked[b] is None:
                     if logits is None:
                         logits = model.rows_logits(len(rows))
                     picked[b] = seq.sampler.sample_with_coin(logits[b], coins[b])
+            if asking:
+                if lp_device:
+                    results = model.rows_logprobs(len(rows))
+                elif logits is None:
+                    logits = model.rows_logits(len(rows))
+                for b, (seq, _, _, smp) in enumerate(rows):
+                    if not smp or seq.logprobs is None:
+                        continue
+                    if lp_device:
+                        entries[b] = _entry_from_device(
+                            results[b], int(picked[b]), sampled[b],
+                            None if sampled[b] is not None else logits[b],
+                            seq.logprobs)
+                    else:
+                        entries[b] = _entry_from_logits(
+                            logits[b], int(picked[b]), seq.logprobs)
         else:
             logits = model.forward_rows(tokens, slots, positions)
             picked = [seq.sampler.sample(logits[b]) if smp else None
                       for b, (seq, _, _, smp) in enumerate(rows)]
+            for b, (seq, _, _, smp) in enumerate(rows):
+                if smp and seq.logprobs is not None:
+                    entries[b] = _entry_from_logits(logits[b], int(picked[b]),
+                                                    seq.logprobs)
         now = time.perf_counter()
         for seq, _, pos, _ in rows:
             if seq.prefilling:
@@ -382,15 +500,23 @@ class BatchEngine:
                 self._register_pages(seq)
         for b, (seq, _, pos, smp) in enumerate(rows):
             if smp:
-                self._accept(seq, int(picked[b]), now)
+                self._accept(seq, int(picked[b]), now, entries[b])
+        if lp_device and asking and not any(seq.logprobs is not None
+                                            for seq in self.running):
+            model.set_logprobs(False)  # the last asking sequence has ended
 
-    def _accept(self, seq: _Sequence, token: int, now: float) -> None:
+    def _accept(self, seq: _Sequence, token: int, now: float,
+                entry: TokenLogprob | None = None) -> None:
         if not seq.out:
             seq.stats.prefill_time = now - seq._t0
             seq._t0 = now  # decode time runs from the first token on
         seq.out.append(token)
         if seq.on_token:
             seq.on_token(token)
+        if entry is not None:
+            seq.stats.logprobs.append(entry)
+            if seq.on_logprobs:
+                seq.on_logprobs(entry)
         # the same three ends as InferenceEngine.generate, in its order
         next_pos = len(seq.prompt) + len(seq.out) - 1
         if (len(seq.out) >= seq.max_tokens

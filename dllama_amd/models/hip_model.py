@@ -52,6 +52,11 @@ from ..quants import Q80, q40_to_planes
 from .config import ModelConfig
 
 QB = 32
+# logprob_rows results per row: f32 {lse, logprob, top-20 logprobs} and i32
+# top-20 ids; with the row's {token, status} that is LP_WORDS int64 words
+LP_MAXK = R.LOGPROB_MAXK
+LP_F32 = 2 + LP_MAXK
+LP_WORDS = 2 + LP_F32 // 2 + LP_MAXK // 2
 
 
 class Linear:
@@ -194,6 +199,16 @@ class HipTransformer:
         self._graph = None
         self._graph_pos = None
         self._graph_samples = False  # the captured graph ends in the sampler
+        # token log-probabilities (set_logprobs): off by default. The graphs
+        # of the setting that is not in force wait in _lp_parked as
+        # (_graph, _graph_samples, _row_graphs), so switching recaptures
+        # nothing that was captured before.
+        self.logprobs = False
+        self._lp_parked = (None, False, {})
+        self._graph_wanted = False  # capture_decode_graph was asked for
+        self._lp_scratch = None
+        self._lp_host = None        # what the last step's one copy brought
+        self._lp_rows_host = None
         self._dev_sampler = None
         self.greedy_feedback = False
         self.skip_logits = False  # prefill chunks before the last skip wcls
@@ -387,7 +402,11 @@ class HipTransformer:
         self._step_in = torch.zeros(NB + 4, dtype=torch.int64, device=dev)
         self.tokens = self._step_in[:NB]
         self.sample_params = self._step_in[NB:].view(torch.float64)
-        self.sample_out = torch.zeros(2, dtype=torch.int64, device=dev)  # token, status
+        # what one step hands back, in one allocation so one copy returns
+        # it: {token, status}, then (set_logprobs) the row's f32 {lse,
+        # logprob, top-20 logprobs} and its i32 top-20 ids
+        self._sample_io = torch.zeros(LP_WORDS, dtype=torch.int64, device=dev)
+        self.sample_out = self._sample_io[:2]  # token, status
         self.x = torch.zeros(NB, c.dim, device=dev)
         self.t_norm = torch.zeros(NB, c.dim, device=dev)
         self.xq = QuantBuf(NB, c.dim, dev)
@@ -938,6 +957,8 @@ class HipTransformer:
         assert B <= self.n_batches
         p0 = self._first_position(positions, B)
         self.tokens[:B].copy_(tokens.to(self.device), non_blocking=True)
+        if B == 1:
+            self._recapture_parked(p0)
         if B == 1 and self._graph is not None:
             self._replay_decode(p0)
         else:
@@ -1025,7 +1046,15 @@ class HipTransformer:
         """Sample from any device f32 logits row, eagerly (first token after
         prefill, --no-graph). None: resample on the host with the same coin
         (Sampler.sample_with_coin)."""
-        return self._sampler().sample(row, coin, temperature, topp)
+        smp = self._sampler()
+        if not self.logprobs:
+            return smp.sample(row, coin, temperature, topp)
+        smp.fill_params(smp.host_params, coin, temperature, topp)
+        smp.params.copy_(smp.host_params, non_blocking=True)
+        row = row.reshape(-1)
+        smp.launch(row)
+        self._launch_logprobs(row, self.sample_out[0:1], self._sample_io)
+        return self._read_sample()
 
     def forward_sample(self, tokens: torch.Tensor, positions: torch.Tensor,
                        coin, temperature: float, topp: float):
@@ -1043,15 +1072,125 @@ class HipTransformer:
         # one staged copy for token and parameters; tokens[1:] are rewritten
         # too (zeros): a B=1 step reads tokens[0] only
         self._step_in.copy_(self._step_host, non_blocking=True)
+        self._recapture_parked(p0)
         if self._graph is not None:
             self._replay_decode(p0)
             if not self._graph_samples:
-                smp.launch(self.last_logits())
+                self._sample_last()
         else:
             self._follow_wide_tier(p0, emit_q80=True)
             self._step_at(1, p0)
-            smp.launch(self.last_logits())
-        return smp.read()
+            self._sample_last()
+        return self._read_sample() if self.logprobs else smp.read()
+
+    def _sample_last(self):
+        """The sampler over the last B=1 step's row and, with set_logprobs,
+        the log-probabilities of what it picked. No host value: capturable."""
+        row = self.last_logits()
+        self._sampler().launch(row)
+        if self.logprobs:
+            self._launch_logprobs(row, self.sample_out[0:1], self._sample_io)
+
+    # ------------------------------------------------------------ logprobs
+
+    def set_logprobs(self, on: bool) -> None:
+        """Report token log-probabilities: every sampler launch is followed
+        by logprob_rows (k = 20, the most a request can ask for, so one graph
+        serves every request) on the token the sampler wrote, and the step's
+        one copy back brings them along (last_logprobs, rows_logprobs). Off
+        (the default) nothing is launched or copied beyond {token, status}.
+        The captured graphs of both settings are kept."""
+        on = bool(on)
+        if on == self.logprobs:
+            return
+        parked = (self._graph, self._graph_samples, self._row_graphs)
+        self._graph, self._graph_samples, self._row_graphs = self._lp_parked
+        self._lp_parked = parked
+        self.logprobs = on
+        if on:
+            self._logprob_scratch()
+
+    def _recapture_parked(self, p0: int):
+        """A decode graph was asked for, and this setting of set_logprobs
+        has none yet (or lost it to a split change while parked): capture it
+        at the position the step is about to run at."""
+        if self._graph is None and self._graph_wanted:
+            self.pos.fill_(p0)
+            self.capture_decode_graph()
+            self.pos.fill_(p0)
+            self._graph_pos = p0
+
+    def _logprob_scratch(self):
+        """Stage A's per-chunk partials for n_batches rows; built on first
+        use (before a capture)."""
+        if self._lp_scratch is None:
+            n = self.n_batches * int(self.k.logprob_chunks(self.cfg.vocab_size))
+            self._lp_scratch = (
+                torch.zeros(2 * n, device=self.device),          # max, sum-exp
+                torch.zeros(LP_MAXK * n, dtype=torch.int64,
+                            device=self.device))                 # chunk top keys
+        return self._lp_scratch
+
+    @staticmethod
+    def _lp_views(io: torch.Tensor, rows: int):
+        """The f32 [rows, 22] and i32 [rows, 20] blocks of a result buffer
+        of rows * LP_WORDS int64 words (after the rows' {token, status})."""
+        a, b = 2 * rows, (2 + LP_F32 // 2) * rows
+        return (io[a:b].view(torch.float32).view(rows, LP_F32),
+                io[b:].view(torch.int32).view(rows, LP_MAXK))
+
+    def _launch_logprobs(self, logits, targets, io, k: int = LP_MAXK):
+        """logprob_rows over `logits` ([V] or [B, V], any row stride) for
+        the device targets, into the blocks of the result buffer `io`."""
+        rows = io.numel() // LP_WORDS
+        self.k.logprob_rows(logits, self.cfg.vocab_size, targets, k,
+                            *self._logprob_scratch(), *self._lp_views(io, rows))
+
+    def _read_sample(self):
+        """forward_sample's one synchronising read with set_logprobs on:
+        {token, status} and the log-probability blocks together."""
+        self._lp_host = host = self._sample_io.cpu()
+        token, status = host[:2].tolist()
+        return None if status else token
+
+    @staticmethod
+    def _lp_entries(host: torch.Tensor, rows: int, B: int) -> list:
+        lp, ids = HipTransformer._lp_views(host, rows)
+        lp, ids = lp[:B].tolist(), ids[:B].tolist()
+        return [(r[0], r[1], i, r[2:]) for r, i in zip(lp, ids)]
+
+    def last_logprobs(self):
+        """(lse, logprob, top_ids[20], top_logprobs[20]) of the token the
+        last sample_row / forward_sample picked, from that step's copy.
+        After a None result `logprob` belongs to a stale token: the caller's
+        resampled token has logit - lse."""
+        if self._lp_host is None:
+            raise RuntimeError("no step has run with set_logprobs(True)")
+        return self._lp_entries(self._lp_host, 1, 1)[0]
+
+    def rows_logprobs(self, B: int) -> list:
+        """last_logprobs for each of the B rows of the last
+        forward_rows_sample."""
+        if self._lp_rows_host is None:
+            raise RuntimeError("no row step has run with set_logprobs(True)")
+        return self._lp_entries(self._lp_rows_host, self.n_batches, B)
+
+    def logprob_targets(self, logits: torch.Tensor, targets) -> list:
+        """log-probability of targets[b] under row b of the device logits
+        [B, V] (one of -1 gives -inf): the same kernels at k = 0, one copy
+        of B floats back. The logits are not copied."""
+        if logits.dim() == 1:
+            logits = logits[None]
+        NB, out = self.n_batches, []
+        for i in range(0, logits.shape[0], NB):
+            chunk = logits[i: i + NB]
+            B = chunk.shape[0]
+            t = torch.tensor([int(x) for x in targets[i: i + B]],
+                             dtype=torch.int64).to(self.device)
+            io = torch.zeros(B * LP_WORDS, dtype=torch.int64, device=self.device)
+            self._launch_logprobs(chunk, t, io, k=0)
+            out += self._lp_views(io, B)[0][:, 1].tolist()
+        return out
 
     # ------------------------------------------------------------ pages
 
@@ -1108,8 +1247,11 @@ class HipTransformer:
                                        self.page_size)
             else:
                 self.row_addr = KVAddr("_rows", self.rows)
-            self.rows_sample_out = torch.zeros(NB, 2, dtype=torch.int64,
-                                               device=dev)  # token, status
+            # [token, status] of every row, then (set_logprobs) the rows'
+            # f32 [NB, 22] and i32 [NB, 20] blocks: one copy returns it all
+            self._rows_out = torch.zeros(NB * LP_WORDS, dtype=torch.int64,
+                                         device=dev)
+            self.rows_sample_out = self._rows_out[:2 * NB].view(NB, 2)
             self._rows_host = torch.zeros(6 * NB, dtype=torch.int64)
             if dev.type == "cuda":
                 self._rows_host = self._rows_host.pin_memory()
@@ -1180,6 +1322,10 @@ class HipTransformer:
         logits = self.rows_logits(B)
         for b in range(B):
             self._row_sampler(b).launch(logits[b])
+        if self.logprobs:
+            # one pair of launches for all B rows, on the tokens just written
+            self._launch_logprobs(logits, self.rows_sample_out[:, 0],
+                                  self._rows_out)
 
     def _capture_rows_graph(self, B: int):
         """Capture an all-decode step of B rows with its per-row samplers
@@ -1245,8 +1391,11 @@ class HipTransformer:
         B, table, decode_only = self._stage_rows(tokens, slots, positions,
                                                  params)
         self._run_rows(B, table, decode_only, sample=True)
-        return [None if status else token
-                for token, status in self.rows_sample_out[:B].tolist()]
+        picked = self.rows_sample_out[:B]
+        if self.logprobs:  # still one synchronising read: everything at once
+            self._lp_rows_host = host = self._rows_out.cpu()
+            picked = host[:2 * self.n_batches].view(-1, 2)[:B]
+        return [None if status else token for token, status in picked.tolist()]
 
     # ------------------------------------------------------------ graphs
 
@@ -1294,6 +1443,7 @@ class HipTransformer:
             self._graph_pos = pos_saved
         self._pf_graphs.clear()  # prefill graphs also reference the scratch
         self._row_graphs.clear()  # and so do the row-step graphs
+        self._lp_parked = (None, False, {})  # ... of either set_logprobs setting
 
     def _capture(self, body, warmups: int, tail=None):
         """The capture procedure: synchronise, run body() `warmups` times on
@@ -1340,13 +1490,16 @@ class HipTransformer:
         sampler runs inside it, between the step and the pos advance."""
         self._rows_only()
         sample = bool(self.device_sampling)
+        self._graph_wanted = True
         if sample:
             self._sampler()  # its buffers exist before anything is captured
+            if self.logprobs:
+                self._logprob_scratch()
 
         def step():
             self.forward_buffers(1)
             if sample:
-                self._sampler().launch(self.last_logits())
+                self._sample_last()
 
         self._graph = self._capture(
             step, warmups=2, tail=lambda: self.k.pos_inc(self.pos, 1))

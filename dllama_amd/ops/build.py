@@ -16,7 +16,7 @@ _EXT_NAME = "dllama_hip"
 # <name>_hip.hip copy beside every source, which a csrc/*.hip glob would
 # pick up on the second build.
 _SOURCES = ("quant_norm.hip", "gemv.hip", "gemm.hip", "attn.hip", "moe.hip",
-            "sync.hip", "sampler.hip", "host.hip", "module.hip")
+            "sync.hip", "sampler.hip", "logprob.hip", "host.hip", "module.hip")
 _HEADER = "dllama_common.h"
 
 

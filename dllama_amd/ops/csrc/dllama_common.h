@@ -17,7 +17,7 @@
 // the Q80 / wire / ssq-slot idioms, host-side checks and the register_*
 // prototypes. Kernels, their launchers and their bindings live in
 //   quant_norm.hip  gemv.hip  gemm.hip  attn.hip  moe.hip  sync.hip
-//   sampler.hip
+//   sampler.hip  logprob.hip
 // host-only code (CPU matmul, BPE encoder) in host.hip, the module in
 // module.hip.
 
@@ -297,4 +297,5 @@ void register_attn(py::module &m);
 void register_moe(py::module &m);
 void register_sync(py::module &m);
 void register_sampler(py::module &m);
+void register_logprob(py::module &m);
 void register_host(py::module &m);

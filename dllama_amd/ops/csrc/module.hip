@@ -10,5 +10,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     register_moe(m);
     register_sync(m);
     register_sampler(m);
+    register_logprob(m);
     register_host(m);
 }

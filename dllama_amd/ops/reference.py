@@ -381,3 +381,42 @@ def sample_ref(logits, temperature: float, topp: float, coin: float):
     margin = min(float(np.abs(c - topp).min()),
                  float(np.abs(c[: last + 1] - r).min() / c[last]))
     return int(order[pick]), margin
+
+
+# ------------------------------------------------------------ log-probabilities
+
+LOGPROB_MAXK = 20
+
+
+def logprob_rows_ref(logits, targets, k: int):
+    """Oracle of the logprob_rows kernel, and the CPU path of everything that
+    reports log-probabilities: per row of `logits` ([B, V] or [V]) returns
+    (lse [B], logprob of targets[b] [B], top-k logprobs [B, 20] descending,
+    top-k ids [B, 20]); float64 values, int64 ids.
+
+    logprob(i) = logits[i] - logsumexp(logits), in float64 on the f32 values:
+    the model's distribution at temperature 1. The order is that of a stable
+    descending sort of the f32 values: lower index first on equal values,
+    -0.0 equal to +0.0. A target outside [0, V) gives -inf; entries past
+    min(k, V) are -inf and -1."""
+    x32 = torch.as_tensor(logits).detach().cpu().float()
+    if x32.dim() == 1:
+        x32 = x32[None]
+    B, V = x32.shape
+    if not 0 <= k <= LOGPROB_MAXK:
+        raise ValueError(f"k must be 0..{LOGPROB_MAXK} (got {k})")
+    x = x32.double()
+    lse = torch.logsumexp(x, dim=-1)
+    t = torch.as_tensor(targets, dtype=torch.int64).reshape(-1).cpu()[:B]
+    valid = (t >= 0) & (t < V)
+    picked = x.gather(1, t.clamp(0, V - 1)[:, None])[:, 0] - lse
+    target_lp = torch.where(valid, picked,
+                            torch.full_like(picked, float("-inf")))
+    top_lp = torch.full((B, LOGPROB_MAXK), float("-inf"), dtype=torch.float64)
+    top_id = torch.full((B, LOGPROB_MAXK), -1, dtype=torch.int64)
+    n = min(k, V)
+    if n:
+        order = torch.sort(x32, dim=-1, stable=True, descending=True).indices[:, :n]
+        top_id[:, :n] = order
+        top_lp[:, :n] = x.gather(1, order) - lse[:, None]
+    return lse, target_lp, top_lp, top_id

@@ -18,6 +18,8 @@ model steps rows only). --context N starts the timed decode at position N:
 the prompt is still --prefill tokens, the cache rows between hold zeros, and
 every step reads all N of them, so long contexts are timed without paying
 B long prefills. --kv-dtype q80 runs either form on the Q80 KV cache.
+--logprobs turns set_logprobs on: every step also computes the rows' token
+log-probabilities (top 20) in the graph and copies them back with the tokens.
 
 Warmup and timing follow bench.py: untimed warmup steps on the shapes of
 the timed window, then a host clock around `--steps` steps ending in a
@@ -57,6 +59,8 @@ def main():
     ap.add_argument("--page-size", type=int, default=64)
     ap.add_argument("--kv-dtype", default=None, choices=["f16", "f32", "q80"],
                     help="KV cache format (default: the model's, f16)")
+    ap.add_argument("--logprobs", action="store_true",
+                    help="set_logprobs(True): log-probabilities in every step")
     args = ap.parse_args()
     context = max(args.context, args.prefill)
     if not torch.cuda.is_available():
@@ -81,6 +85,7 @@ def main():
     model =HipTransformer.synthetic(cfg, device=device, n_slots=max(batches),
                                      **paging)
     model.device_sampling = True
+    model.set_logprobs(args.logprobs)
     torch.cuda.synchronize(device)
     print(f"# built synthetic {args.model} with {model.n_slots} KV slots in "
           f"{time.time() - t0:.1f}s", file=sys.stderr)
@@ -172,6 +177,7 @@ def main():
                    "kv_dtype": model.kv_dtype,
                    "kv_cache_bytes": model.kv_cache_bytes(),
                    "sampling": "on device, temperature 0",
+                   "logprobs": args.logprobs,
                    "data": "synthetic (random-init weights, random prompt)"},
     }))
 
