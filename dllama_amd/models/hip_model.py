@@ -32,13 +32,15 @@ value also names a device page table: the cache is a pool of pages and each
 slot reaches its rows through it. With the default of one slot nothing of
 this is allocated or launched.
 
-Whatever is captured as a hipGraph (the decode step, a full prefill chunk,
-an all-decode row step) goes through one procedure, `_capture`.
+Which steps replay a captured hipGraph is asked of one store, `self.graphs`
+(models/graphs.py); the step that first needs a graph captures it.
 """
 
 from __future__ import annotations
 
 import os
+import sys
+from functools import partial
 
 import numpy as np
 import torch
@@ -50,6 +52,7 @@ from ..ops.sampler import DeviceSampler
 from ..parallel.comm import Comm, SingleComm
 from ..quants import Q80, q40_to_planes
 from .config import ModelConfig
+from .graphs import StepGraphs, capture_hip_graph
 
 QB = 32
 # logprob_rows results per row: f32 {lse, logprob, top-20 logprobs} and i32
@@ -196,27 +199,23 @@ class HipTransformer:
         self.embedding = None
         self.final_norm = None
         self.wcls = None
-        self._graph = None
-        self._graph_pos = None
-        self._graph_samples = False  # the captured graph ends in the sampler
-        # token log-probabilities (set_logprobs): off by default. The graphs
-        # of the setting that is not in force wait in _lp_parked as
-        # (_graph, _graph_samples, _row_graphs), so switching recaptures
-        # nothing that was captured before.
-        self.logprobs = False
-        self._lp_parked = (None, False, {})
+        # every captured graph, valid at the attn_splits in force
+        # (no reference back to the model: a cycle would leave a dropped
+        # model, graphs and all, to a garbage collection mid-capture)
+        self.graphs = StepGraphs(partial(capture_hip_graph, self.device),
+                                 on_gpu=self.device.type == "cuda")
+        self._graph_pos = None      # where the decode graph left the device pos
         self._graph_wanted = False  # capture_decode_graph was asked for
+        self.row_graphs = True      # capture all-decode forward_rows steps
+        # token log-probabilities (set_logprobs): off by default; part of
+        # a graph's key, so switching recaptures nothing
+        self.logprobs = False
         self._lp_scratch = None
         self._lp_host = None        # what the last step's one copy brought
         self._lp_rows_host = None
         self._dev_sampler = None
         self.greedy_feedback = False
         self.skip_logits = False  # prefill chunks before the last skip wcls
-        self._pf_graphs = {}      # skip_logits -> captured 32-token graph
-        self._pf_failed = False
-        self.row_graphs = True    # capture all-decode forward_rows steps
-        self._row_graphs = {}     # B -> captured all-decode row step
-        self._row_graphs_failed = False
         self._rows_io = None      # row-step staging, built on first use
         # per-model constants
         self.kv_mul = c.n_heads0 // max(1, c.kv_dim0 // c.head_dim)
@@ -958,18 +957,17 @@ class HipTransformer:
         p0 = self._first_position(positions, B)
         self.tokens[:B].copy_(tokens.to(self.device), non_blocking=True)
         if B == 1:
-            self._recapture_parked(p0)
-        if B == 1 and self._graph is not None:
-            self._replay_decode(p0)
+            self._decode_step(p0)
         else:
             self._follow_wide_tier(
                 p0 + B - 1, emit_q80=not (B >= 8 and self.prefill_bf16))
             g = None
-            if B == self.n_batches and not self._pf_failed:
+            if B == self.n_batches:
                 # full prefill chunks replay a captured graph (eager chunk
-                # cost is host-launch-bound: ~400 python kernel launches)
-                g = (self._pf_graphs.get(self.skip_logits)
-                     or self._capture_prefill_graph(self.skip_logits))
+                # cost is host-launch-bound: ~400 python kernel launches);
+                # where capture is unsupported they run eager, silently
+                g = self.graphs.get(("prefill", self.skip_logits), lambda: (
+                    lambda: self.forward_buffers(B), 1, None, None))
             self._step_at(B, p0, g)
         if self.tp_path:
             NBp = _pow2_batch(B)
@@ -1009,15 +1007,31 @@ class HipTransformer:
         if wide != (self.attn_splits == 1):
             self._set_attn_splits(1 if wide else self._splits_above)
 
-    def _replay_decode(self, p0: int):
-        """One replay of the captured decode graph on tokens[0] at p0."""
-        sp = self._pick_splits(p0)
-        if sp != self.attn_splits:
-            self._set_attn_splits(sp)  # recapture at the new K-split count
-        if p0 != self._graph_pos:
-            self.pos.fill_(p0)
-        self._graph.replay()
+    def _decode_step(self, p0: int) -> bool:
+        """One B=1 step at p0: a replay of the decode graph, captured here at
+        p0's K-split count if wanted and absent, else eager. True: it sampled."""
+        key, g = ("decode", self.logprobs), None
+        if self.graphs.allowed("decode", self._graph_wanted):
+            sp = self._pick_splits(p0)
+            if sp != self.attn_splits:
+                self._set_attn_splits(sp)  # drops the graphs of the old count
+            if p0 != self._graph_pos:
+                # before a capture too: its warmups write the KV row of pos
+                self.pos.fill_(p0)
+            g = self.graphs.get(key, self._decode_plan, on_error=lambda e:
+                                self._capture_failed("decode", e))
+        if g is None:
+            self._follow_wide_tier(p0, emit_q80=True)
+            self._step_at(1, p0)
+            return False
+        g.replay()
         self._graph_pos = p0 + 1  # the graph's pos_inc advanced it
+        return self.graphs.entries[key][1]
+
+    def _capture_failed(self, what: str, e: Exception):
+        if self.comm.rank == 0:
+            print(f"⚠️  {what} graph capture failed ({e}); "
+                  "running eager (slower)", file=sys.stderr)
 
     # ------------------------------------------------------------ sampling
 
@@ -1037,8 +1051,9 @@ class HipTransformer:
             self._dev_sampler = DeviceSampler(
                 self.cfg.vocab_size, self.device, params=self.sample_params,
                 out=self.sample_out, k=self.k)
-            self._step_host = torch.zeros(self.n_batches + 4,
-                                          dtype=torch.int64).pin_memory()
+            self._step_host = torch.zeros(self.n_batches + 4, dtype=torch.int64)
+            if self.device.type == "cuda":
+                self._step_host = self._step_host.pin_memory()
         return self._dev_sampler
 
     def sample_row(self, row: torch.Tensor, coin, temperature: float,
@@ -1072,14 +1087,7 @@ class HipTransformer:
         # one staged copy for token and parameters; tokens[1:] are rewritten
         # too (zeros): a B=1 step reads tokens[0] only
         self._step_in.copy_(self._step_host, non_blocking=True)
-        self._recapture_parked(p0)
-        if self._graph is not None:
-            self._replay_decode(p0)
-            if not self._graph_samples:
-                self._sample_last()
-        else:
-            self._follow_wide_tier(p0, emit_q80=True)
-            self._step_at(1, p0)
+        if not self._decode_step(p0):
             self._sample_last()
         return self._read_sample() if self.logprobs else smp.read()
 
@@ -1099,26 +1107,10 @@ class HipTransformer:
         serves every request) on the token the sampler wrote, and the step's
         one copy back brings them along (last_logprobs, rows_logprobs). Off
         (the default) nothing is launched or copied beyond {token, status}.
-        The captured graphs of both settings are kept."""
-        on = bool(on)
-        if on == self.logprobs:
-            return
-        parked = (self._graph, self._graph_samples, self._row_graphs)
-        self._graph, self._graph_samples, self._row_graphs = self._lp_parked
-        self._lp_parked = parked
-        self.logprobs = on
+        The captured graphs of both settings are kept (it is in their key)."""
+        self.logprobs = bool(on)
         if on:
             self._logprob_scratch()
-
-    def _recapture_parked(self, p0: int):
-        """A decode graph was asked for, and this setting of set_logprobs
-        has none yet (or lost it to a split change while parked): capture it
-        at the position the step is about to run at."""
-        if self._graph is None and self._graph_wanted:
-            self.pos.fill_(p0)
-            self.capture_decode_graph()
-            self.pos.fill_(p0)
-            self._graph_pos = p0
 
     def _logprob_scratch(self):
         """Stage A's per-chunk partials for n_batches rows; built on first
@@ -1327,24 +1319,11 @@ class HipTransformer:
             self._launch_logprobs(logits, self.rows_sample_out[:, 0],
                                   self._rows_out)
 
-    def _capture_rows_graph(self, B: int):
-        """Capture an all-decode step of B rows with its per-row samplers
-        and the table advance; None (and eager from then on) where capture
-        is unsupported."""
-        try:
-            for b in range(B):
-                self._row_sampler(b)  # buffers exist before the capture
-            g = self._capture(lambda: self._rows_step_and_sample(B), warmups=2,
-                              tail=lambda: self.k.rows_advance(self.rows, B))
-            self._row_graphs[B] = g
-            return g
-        except Exception as e:  # noqa: BLE001
-            import sys
-            if self.comm.rank == 0:
-                print(f"⚠️  row-step graph capture failed ({e}); "
-                      "running eager (slower)", file=sys.stderr)
-            self._row_graphs_failed = True
-            return None
+    def _rows_plan(self, B: int):
+        """B all-decode rows and their samplers; the tail advances the table."""
+        self._row_sampler(B - 1)  # buffers exist before the capture
+        return (lambda: self._rows_step_and_sample(B), 2,
+                lambda: self.k.rows_advance(self.rows, B), None)
 
     def _run_rows(self, B: int, table, decode_only: bool, sample: bool):
         """The staged step: a replay of the B-row graph when every row is a
@@ -1352,11 +1331,10 @@ class HipTransformer:
         sp = self._pick_splits(max(p for _, p in table), rows=True)
         if sp != self.attn_splits:
             self._set_attn_splits(sp)  # drops the row graphs with the scratch
-        g = None
-        if (decode_only and self.row_graphs and not self._row_graphs_failed
-                and self.device.type == "cuda"):
-            g = self._row_graphs.get(B) or self._capture_rows_graph(B)
-        if g is not None:
+        g = decode_only and self.graphs.get(
+            ("rows", B, self.logprobs), lambda: self._rows_plan(B),
+            self.row_graphs, lambda e: self._capture_failed("row-step", e))
+        if g:
             g.replay()
             # the graph's rows_advance moved every row on
             self._rows_dev[:B] = [(base, p + 1) for base, p in table]
@@ -1428,80 +1406,48 @@ class HipTransformer:
 
     def _set_attn_splits(self, s: int):
         """Switch the flash-decode K-split count mid-stream (long-context
-        adaptivity): resize the split scratch and recapture the decode
-        graph. Decode state (KV caches, device pos) is untouched; the
-        capture warmup's KV write at the current pos is overwritten by the
-        next real step."""
+        adaptivity): resize the split scratch and drop every captured graph,
+        which names it. Decode state (KV caches, device pos) is untouched."""
         self.attn_splits = s
         if s != 1:
             self._splits_above = s
         self._alloc_attn_scratch()
-        if self._graph is not None:
-            pos_saved = int(self.pos.item())
-            self.capture_decode_graph()
-            self.pos.fill_(pos_saved)
-            self._graph_pos = pos_saved
-        self._pf_graphs.clear()  # prefill graphs also reference the scratch
-        self._row_graphs.clear()  # and so do the row-step graphs
-        self._lp_parked = (None, False, {})  # ... of either set_logprobs setting
+        self.graphs.clear()
 
-    def _capture(self, body, warmups: int, tail=None):
-        """The capture procedure: synchronise, run body() `warmups` times on
-        a side stream (allocations, lazy kernel loads), join and
-        synchronise, then capture body() and tail() as a hipGraph. The tail
-        (a position advance) is captured but never run while warming up.
-        Buffers that body() would create exist before this is called."""
-        dev = self.device
-        torch.cuda.synchronize(dev)
-        s = torch.cuda.Stream(dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for _ in range(warmups):
-                body()
-        torch.cuda.current_stream(dev).wait_stream(s)
-        torch.cuda.synchronize(dev)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            body()
-            if tail is not None:
-                tail()
-        return g
-
-    def _capture_prefill_graph(self, skip_logits: bool):
-        try:
-            saved = self.skip_logits
-            self.skip_logits = skip_logits
-            g = self._capture(lambda: self.forward_buffers(self.n_batches),
-                              warmups=1)
-            self.skip_logits = saved
-            self._pf_graphs[skip_logits] = g
-            return g
-        except Exception:  # noqa: BLE001
-            # capture unsupported here: prefill chunks run eagerly from now on
-            self._pf_failed = True
-            self.skip_logits = skip_logits
-            return None
-
-    def capture_decode_graph(self):
-        """Capture the whole B=1 decode step (forward + pos advance) as a
-        hipGraph; each subsequent decode costs one graph replay
-        (the HIP analog of the reference's recorded Vulkan command buffers,
-        nn-vulkan.cpp:1065-1118). With device_sampling the temperature/top-p
-        sampler runs inside it, between the step and the pos advance."""
-        self._rows_only()
+    def _decode_plan(self):
+        """The decode graph's plan; its note says whether it samples."""
         sample = bool(self.device_sampling)
-        self._graph_wanted = True
-        if sample:
-            self._sampler()  # its buffers exist before anything is captured
-            if self.logprobs:
-                self._logprob_scratch()
+        if sample:  # its buffers exist before anything is captured
+            self._sampler()
 
         def step():
             self.forward_buffers(1)
             if sample:
                 self._sample_last()
 
-        self._graph = self._capture(
-            step, warmups=2, tail=lambda: self.k.pos_inc(self.pos, 1))
-        self._graph_samples = sample
+        return step, 2, lambda: self.k.pos_inc(self.pos, 1), sample
+
+    def capture_decode_graph(self):
+        """From now on a B=1 step is one replay of a hipGraph of the whole
+        decode step: forward, with device_sampling the sampler, pos advance
+        (the HIP analog of the reference's recorded Vulkan command buffers,
+        nn-vulkan.cpp:1065-1118). Captures it, or raises and steps run eager."""
+        self._rows_only()
+        self._graph_wanted = True
+        self.graphs.capture(("decode", self.logprobs), self._decode_plan)
         self._graph_pos = None  # device pos unknown until first fill
+
+    # what the store holds for the set_logprobs setting in force, read-only
+    # (the benchmark replays _graph itself; tests look at all three)
+    @property
+    def _graph(self):
+        return self.graphs.get(("decode", self.logprobs))
+
+    @property
+    def _graph_samples(self) -> bool:
+        return bool(self._graph and self.graphs.entries["decode", self.logprobs][1])
+
+    @property
+    def _row_graphs(self) -> dict:
+        return {k[1]: e[0] for k, e in self.graphs.entries.items()
+                if k[0] == "rows" and k[2] == self.logprobs}

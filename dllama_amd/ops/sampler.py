@@ -34,7 +34,9 @@ class DeviceSampler:
             torch.zeros(int(k.sampler_max_candidates()),
                         dtype=torch.int64, device=dev),         # candidate sort keys
             torch.zeros(1, dtype=torch.int32, device=dev))      # candidate counter
-        self.host_params = torch.zeros(4, dtype=torch.float64).pin_memory()
+        self.host_params = torch.zeros(4, dtype=torch.float64)
+        if dev.type == "cuda":
+            self.host_params = self.host_params.pin_memory()
 
     @staticmethod
     def fill_params(dst: torch.Tensor, coin, temperature: float, topp: float):

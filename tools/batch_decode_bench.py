@@ -138,7 +138,8 @@ def main():
             state["pos"] += 1
 
         elapsed = timed(step)
-        assert B in model._row_graphs, "the timed steps were not graph replays"
+        assert model.graphs.get(("rows", B, model.logprobs)) is not None, \
+            "the timed steps were not graph replays"
         rows[str(B)] = entry(elapsed, B)
         print(f"# B={B}: {rows[str(B)]}", file=sys.stderr)
 

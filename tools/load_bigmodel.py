@@ -56,14 +56,15 @@ def main():
 
     model.greedy_feedback = True
     model.capture_decode_graph()
+    graph = model.graphs.get(("decode", False))
     model.pos.fill_(0)
     model.tokens[0] = 7
     for _ in range(5):
-        model._graph.replay()
+        graph.replay()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        model._graph.replay()
+        graph.replay()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print(f"decode: {args.steps / dt:.1f} tok/s ({dt / args.steps * 1000:.2f} ms/tok) "

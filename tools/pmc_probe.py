@@ -9,7 +9,7 @@ from dllama_amd.models.hip_model import HipTransformer
 h = preset_header("llama-3.1-8b", seq_len=4096)
 cfg = ModelConfig.from_header(h)
 m = HipTransformer.synthetic(cfg)
-m._pf_failed = True  # eager everywhere so PMC sees plain dispatches
+m.graphs.failed.add("prefill")  # eager everywhere so PMC sees plain dispatches
 m.forward(torch.randint(0, 128256, (32,)), torch.arange(32))   # prefill chunk
 for step in range(4):                                           # decode steps
     m.forward(torch.tensor([7 + step]), torch.tensor([32 + step]))

@@ -73,18 +73,19 @@ def end_to_end(name, args, logit_std):
     from dllama_amd.tokenizer import Sampler
     model, prompt = build(name, args.seq_len, logit_std)
     model.forward(prompt, torch.arange(32))
-    # two graphs over the same buffers: with and without the sampler
-    graphs = {}
+    # two graphs over the same buffers: with and without the sampler,
+    # taken out of the model's store and put back for each window
+    DECODE, graphs = ("decode", False), {}
     for mode, on in (("device", True), ("host", False)):
         model.device_sampling = on
         model.capture_decode_graph()
-        graphs[mode] = (model._graph, model._graph_samples)
+        graphs[mode] = model.graphs.entries.pop(DECODE)
     sampler = Sampler(model.cfg.vocab_size, T, TOPP, 12345)
     eng = InferenceEngine(model, sampler=sampler)
     stats = {"cands": [], "fallbacks": 0, "steps": 0}
 
     def window(mode, n):
-        model._graph, model._graph_samples = graphs[mode]
+        model.graphs.entries[DECODE] = graphs[mode]
         model._graph_pos = None
         model.device_sampling = mode == "device"
         eng.reset(32)
@@ -105,7 +106,7 @@ def end_to_end(name, args, logit_std):
     # outside the timed windows: how many candidates these logits give and
     # how often the device sampler gives up
     eng.reset(32)
-    model._graph, model._graph_samples = graphs["device"]
+    model.graphs.entries[DECODE] = graphs["device"]
     model._graph_pos = None
     token = 7
     for i in range(20):

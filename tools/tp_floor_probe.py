@@ -27,14 +27,15 @@ def run(force_sync):
     m.greedy_feedback = True
     m.forward(torch.randint(0, 128256, (32,)), torch.arange(32))
     m.capture_decode_graph()
+    graph = m.graphs.get(("decode", False))
     m.pos.fill_(32)
     m.tokens[0] = 7
     for _ in range(30):
-        m._graph.replay()
+        graph.replay()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(200):
-        m._graph.replay()
+        graph.replay()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / 200
     del m
