@@ -29,6 +29,72 @@ __device__ __forceinline__ int q40_block_dot(const uint4 wq, const int4 x0,
     return idot;
 }
 
+// The streaming loop of the grouped and SwiGLU kernels: R weight rows
+// against one Q80 activation row of n elements (codes xq, block scales xs,
+// block sums xbs), into acc[R]. Lane `lane` of `nlanes` takes the block
+// pairs lane, lane + nlanes, ...; lane 0 takes the odd trailing block.
+// Every accumulator is fed block 2jp, then 2jp + 1, jp ascending, then the
+// trailing block, one fmaf each: the integer dots are exact, so this order
+// alone fixes the bits of the result. All R rows' weights of a trip are
+// loaded ahead of the activations (see RPW at k_q40_gemv). k_q40_gemv runs
+// the same loop over NB activation rows and a K slice, in its own body: as
+// a call to a function like this one its batch-1 forms came out of hipcc
+// with 66 VGPRs in place of 60 (7 waves per SIMD in place of 8), whatever
+// the order of the statements here (profiles/r13_gemv_core.md).
+template <int R>
+__device__ __forceinline__ void q40_q80_rows_dot(
+        const uint4 *const (&wrow)[R], const __half *const (&srow)[R],
+        const int8_t *xq, const float *xs, const float *xbs, int n,
+        int lane, int nlanes, float (&acc)[R]) {
+    const int nb = n / QB;
+    for (int jp = lane; jp < (nb >> 1); jp += nlanes) {
+        const int j = jp << 1;
+        uint4 wq0[R], wq1[R];
+        float2 sw[R];
+        #pragma unroll
+        for (int r = 0; r < R; r++) {
+            wq0[r] = wrow[r][j];
+            wq1[r] = wrow[r][j + 1];
+            sw[r] = __half22float2(*reinterpret_cast<const __half2 *>(srow[r] + j));
+        }
+        const int4 *xrow = reinterpret_cast<const int4 *>(xq) + j * 2;
+        const int4 x0 = xrow[0], x1 = xrow[1], x2 = xrow[2], x3 = xrow[3];
+        const float2 sx = *reinterpret_cast<const float2 *>(xs + j);
+        const float2 bsum = *reinterpret_cast<const float2 *>(xbs + j);
+        #pragma unroll
+        for (int r = 0; r < R; r++) {
+            const int idot0 = q40_block_dot(wq0[r], x0, x1);
+            const int idot1 = q40_block_dot(wq1[r], x2, x3);
+            acc[r] = fmaf(sw[r].x * sx.x, (float)idot0 - 8.0f * bsum.x, acc[r]);
+            acc[r] = fmaf(sw[r].y * sx.y, (float)idot1 - 8.0f * bsum.y, acc[r]);
+        }
+    }
+    if ((nb & 1) && lane == 0) {  // odd trailing block
+        const int j = nb - 1;
+        const int4 *xb = reinterpret_cast<const int4 *>(xq) + j * 2;
+        #pragma unroll
+        for (int r = 0; r < R; r++)
+            acc[r] = fmaf(__half2float(srow[r][j]) * xs[j],
+                          (float)q40_block_dot(wrow[r][j], xb[0], xb[1]) - 8.0f * xbs[j],
+                          acc[r]);
+    }
+}
+
+// the in-kernel MoE gate: every wave recomputes the deterministic top-k from
+// the router logits of its batch row and takes entry `want` — removes the
+// k_moe_gate launch from the chain. Whole-wave call.
+__device__ __forceinline__ int moe_gate_expert(const float *router_row, int n_experts,
+                                               int topk, int lane, int want) {
+    int gi[16];
+    float gw[16];
+    moe_gate_wave(router_row, n_experts, topk, lane, gi, gw);
+    int e = 0;
+    #pragma unroll
+    for (int t = 0; t < 16; t++)
+        if (t == want) e = gi[t];
+    return e;
+}
+
 // GEMV epilogue modes: fusing the ops that FOLLOW a matmul into its tail
 // removes whole kernels from the per-layer chain (the reference runs each
 // as its own op, llm.cpp:263-557).
@@ -427,57 +493,27 @@ __global__ void k_q40_gemv_grouped(const uint8_t *__restrict__ qs,
     const int row0 = valid ? wave_row0 + grp * 2 : 0;
     const int lane = full_lane % LPP;
     const int nb = n / QB;
-    const int nbp = nb >> 1;
     int e;
     if constexpr (GATE) {
-        // in-kernel gate: each wave recomputes the deterministic top-k from
-        // the router logits — removes the k_moe_gate launch from the chain
-        int gi[16];
-        float gw[16];
-        const int br = slot / topk, want = slot - br * topk;
-        moe_gate_wave(router + (int64_t)br * n_experts, n_experts, topk,
-                      full_lane, gi, gw);
-        e = 0;
-        #pragma unroll
-        for (int t = 0; t < 16; t++)
-            if (t == want) e = gi[t];
+        const int br = slot / topk;
+        e = moe_gate_expert(router + (int64_t)br * n_experts, n_experts, topk,
+                            full_lane, slot - br * topk);
     } else {
         e = expert_idx[slot];
     }
     const int b = slot / k_slots;
-    const int row1 = min(row0 + 1, d - 1);
-    const uint4 *wrow0 = reinterpret_cast<const uint4 *>(
-        qs + ((int64_t)e * d + row0) * (n >> 1));
-    const uint4 *wrow1 = reinterpret_cast<const uint4 *>(
-        qs + ((int64_t)e * d + row1) * (n >> 1));
-    const __half *srow0 = scales + ((int64_t)e * d + row0) * nb;
-    const __half *srow1 = scales + ((int64_t)e * d + row1) * nb;
-    float acc0 = 0.0f, acc1 = 0.0f;
-    for (int jp = lane; jp < nbp; jp += LPP) {
-        const int j = jp << 1;
-        const uint4 a0 = wrow0[j], a1 = wrow0[j + 1];
-        const uint4 b0 = wrow1[j], b1 = wrow1[j + 1];
-        const float2 sw0 = __half22float2(*reinterpret_cast<const __half2 *>(srow0 + j));
-        const float2 sw1 = __half22float2(*reinterpret_cast<const __half2 *>(srow1 + j));
-        const int4 *xr = reinterpret_cast<const int4 *>(xq + (int64_t)b * n) + j * 2;
-        const int4 x0 = xr[0], x1 = xr[1], x2 = xr[2], x3 = xr[3];
-        const float2 sx = *reinterpret_cast<const float2 *>(xs + (int64_t)b * nb + j);
-        const float2 bsum = *reinterpret_cast<const float2 *>(xbs + (int64_t)b * nb + j);
-        acc0 = fmaf(sw0.x * sx.x, (float)q40_block_dot(a0, x0, x1) - 8.0f * bsum.x, acc0);
-        acc0 = fmaf(sw0.y * sx.y, (float)q40_block_dot(a1, x2, x3) - 8.0f * bsum.y, acc0);
-        acc1 = fmaf(sw1.x * sx.x, (float)q40_block_dot(b0, x0, x1) - 8.0f * bsum.x, acc1);
-        acc1 = fmaf(sw1.y * sx.y, (float)q40_block_dot(b1, x2, x3) - 8.0f * bsum.y, acc1);
+    const uint4 *wrow[2];
+    const __half *srow[2];
+    #pragma unroll
+    for (int r = 0; r < 2; r++) {
+        const int64_t row = (int64_t)e * d + min(row0 + r, d - 1);
+        wrow[r] = reinterpret_cast<const uint4 *>(qs + row * (n >> 1));
+        srow[r] = scales + row * nb;
     }
-    if ((nb & 1) && lane == 0) {  // odd trailing block
-        const int j = nb - 1;
-        const int4 *xb = reinterpret_cast<const int4 *>(xq + (int64_t)b * n) + j * 2;
-        acc0 = fmaf(__half2float(srow0[j]) * xs[(int64_t)b * nb + j],
-                    (float)q40_block_dot(wrow0[j], xb[0], xb[1])
-                    - 8.0f * xbs[(int64_t)b * nb + j], acc0);
-        acc1 = fmaf(__half2float(srow1[j]) * xs[(int64_t)b * nb + j],
-                    (float)q40_block_dot(wrow1[j], xb[0], xb[1])
-                    - 8.0f * xbs[(int64_t)b * nb + j], acc1);
-    }
+    float acc[2] = {};
+    q40_q80_rows_dot<2>(wrow, srow, xq + (int64_t)b * n, xs + (int64_t)b * nb,
+                        xbs + (int64_t)b * nb, n, lane, LPP, acc);
+    float acc0 = acc[0], acc1 = acc[1];
     #pragma unroll
     for (int o = LPP / 2; o > 0; o >>= 1) {
         acc0 += __shfl_down(acc0, o, WAVE);
@@ -504,80 +540,15 @@ __global__ void k_q40_gemv_grouped(const uint8_t *__restrict__ qs,
 // silu(a)*g values assemble in LDS and the first 32 lanes quantize.
 // (reference runs matmul w1, matmul w3, silu, mul, cast as 5 ops,
 // llm.cpp:430-448 / nn-cpu-ops.cpp:462-500.)
-template <bool GELU>
+// GROUPED is the MoE form, with the gate computed in-kernel from the router
+// logits: for decode (B=1) this single launch replaces moe_gate + grouped
+// w13 GEMV + swiglu_q80 (reference runs repeat_z, gate matmul, softmax,
+// moe_gate, grouped w1/w3, silu, mul, cast — llm.cpp:450-487). Weights
+// [E, 2*ff, n/2], workgroup = one Q80 block of expert slot blockIdx.y's
+// output, oq/os/obs [n_slots, ff]. The dense form is expert 0, x row 0,
+// slot 0.
+template <bool GELU, bool GROUPED>
 __global__ __launch_bounds__(1024) void k_q40_gemv_swiglu(
-        const uint8_t *__restrict__ qs, const __half *__restrict__ scales,
-        const int8_t *__restrict__ xq, const float *__restrict__ xs,
-        const float *__restrict__ xbs, int ff, int n,
-        int8_t *__restrict__ oq, float *__restrict__ os,
-        float *__restrict__ obs) {
-    const int wave = threadIdx.x / WAVE;  // 16 waves, 2 ff indices each
-    const int lane = threadIdx.x % WAVE;
-    const int i0 = blockIdx.x * 32 + 2 * wave;
-    const int nb = n / QB, nbp = nb >> 1;
-    const int rows[4] = {i0, i0 + 1, ff + i0, ff + i0 + 1};
-    const uint4 *wrow[4];
-    const __half *srow[4];
-    #pragma unroll
-    for (int r = 0; r < 4; r++) {
-        wrow[r] = reinterpret_cast<const uint4 *>(qs + (int64_t)rows[r] * (n >> 1));
-        srow[r] = scales + (int64_t)rows[r] * nb;
-    }
-    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    for (int jp = lane; jp < nbp; jp += WAVE) {
-        const int j = jp << 1;
-        const int4 *xr = reinterpret_cast<const int4 *>(xq) + j * 2;
-        const int4 x0 = xr[0], x1 = xr[1], x2 = xr[2], x3 = xr[3];
-        const float2 sx = *reinterpret_cast<const float2 *>(xs + j);
-        const float2 bsum = *reinterpret_cast<const float2 *>(xbs + j);
-        #pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const uint4 w0 = wrow[r][j], w1 = wrow[r][j + 1];
-            const float2 sw = __half22float2(*reinterpret_cast<const __half2 *>(srow[r] + j));
-            acc[r] = fmaf(sw.x * sx.x, (float)q40_block_dot(w0, x0, x1) - 8.0f * bsum.x, acc[r]);
-            acc[r] = fmaf(sw.y * sx.y, (float)q40_block_dot(w1, x2, x3) - 8.0f * bsum.y, acc[r]);
-        }
-    }
-    if ((nb & 1) && lane == 0) {  // odd trailing block
-        const int j = nb - 1;
-        const int4 *xb = reinterpret_cast<const int4 *>(xq) + j * 2;
-        const float sx1 = xs[j], bs1 = xbs[j];
-        #pragma unroll
-        for (int r = 0; r < 4; r++)
-            acc[r] = fmaf(__half2float(srow[r][j]) * sx1,
-                          (float)q40_block_dot(wrow[r][j], xb[0], xb[1]) - 8.0f * bs1,
-                          acc[r]);
-    }
-    #pragma unroll
-    for (int r = 0; r < 4; r++) acc[r] = wave_reduce_sum(acc[r]);
-    __shared__ float sv[32];
-    if (lane == 0) {
-        #pragma unroll
-        for (int t = 0; t < 2; t++) {
-            const float av = acc[t], gv = acc[2 + t];
-            const float act = GELU
-                ? 0.5f * av * (1.0f + tanhf(0.797884560802865f * (av + 0.044715f * av * av * av)))
-                : av / (1.0f + __expf(-av));
-            sv[2 * wave + t] = act * gv;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 32) {
-        const Q80Lane c = q80_quant_group32(sv[threadIdx.x]);
-        oq[(int64_t)blockIdx.x * QB + threadIdx.x] = (int8_t)c.qf;
-        const float bsum = group32_reduce_sum(c.qf);
-        if (threadIdx.x == 0) { os[blockIdx.x] = c.d; obs[blockIdx.x] = bsum; }
-    }
-}
-
-// grouped (MoE) variant of the fused W1|W3 GEMV + SwiGLU + Q80 emit, with
-// the gate computed in-kernel from the router logits: for decode (B=1) this
-// single launch replaces moe_gate + grouped w13 GEMV + swiglu_q80
-// (reference runs repeat_z, gate matmul, softmax, moe_gate, grouped w1/w3,
-// silu, mul, cast — llm.cpp:450-487). Workgroup = one Q80 block of one
-// expert slot's output.
-template <bool GELU>
-__global__ __launch_bounds__(1024) void k_q40_gemv_grouped_swiglu(
         const uint8_t *__restrict__ qs, const __half *__restrict__ scales,
         const int8_t *__restrict__ xq, const float *__restrict__ xs,
         const float *__restrict__ xbs, int ff, int n,
@@ -586,54 +557,27 @@ __global__ __launch_bounds__(1024) void k_q40_gemv_grouped_swiglu(
         float *__restrict__ obs) {
     const int wave = threadIdx.x / WAVE;  // 16 waves, 2 ff indices each
     const int lane = threadIdx.x % WAVE;
-    const int slot = blockIdx.y;
-    const int br = slot / topk, want = slot - br * topk;
-    int gi[16];
-    float gw[16];
-    moe_gate_wave(router + (int64_t)br * n_experts, n_experts, topk, lane, gi, gw);
-    int e = 0;
-    #pragma unroll
-    for (int t = 0; t < 16; t++)
-        if (t == want) e = gi[t];
+    int slot = 0, br = 0, e = 0;
+    if constexpr (GROUPED) {
+        slot = blockIdx.y;
+        br = slot / topk;
+        e = moe_gate_expert(router + (int64_t)br * n_experts, n_experts, topk,
+                            lane, slot - br * topk);
+    }
     const int i0 = blockIdx.x * 32 + 2 * wave;
-    const int nb = n / QB, nbp = nb >> 1;
+    const int nb = n / QB;
     const int rows[4] = {i0, i0 + 1, ff + i0, ff + i0 + 1};
     const uint4 *wrow[4];
     const __half *srow[4];
     #pragma unroll
     for (int r = 0; r < 4; r++) {
-        const int64_t rbase = (int64_t)e * 2 * ff + rows[r];
-        wrow[r] = reinterpret_cast<const uint4 *>(qs + rbase * (n >> 1));
-        srow[r] = scales + rbase * nb;
+        const int64_t row = (int64_t)e * 2 * ff + rows[r];
+        wrow[r] = reinterpret_cast<const uint4 *>(qs + row * (n >> 1));
+        srow[r] = scales + row * nb;
     }
-    const int8_t *xrow = xq + (int64_t)br * n;
-    const float *xsr = xs + (int64_t)br * nb;
-    const float *xbr = xbs + (int64_t)br * nb;
-    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    for (int jp = lane; jp < nbp; jp += WAVE) {
-        const int j = jp << 1;
-        const int4 *xr = reinterpret_cast<const int4 *>(xrow) + j * 2;
-        const int4 x0 = xr[0], x1 = xr[1], x2 = xr[2], x3 = xr[3];
-        const float2 sx = *reinterpret_cast<const float2 *>(xsr + j);
-        const float2 bsum = *reinterpret_cast<const float2 *>(xbr + j);
-        #pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const uint4 w0 = wrow[r][j], w1 = wrow[r][j + 1];
-            const float2 sw = __half22float2(*reinterpret_cast<const __half2 *>(srow[r] + j));
-            acc[r] = fmaf(sw.x * sx.x, (float)q40_block_dot(w0, x0, x1) - 8.0f * bsum.x, acc[r]);
-            acc[r] = fmaf(sw.y * sx.y, (float)q40_block_dot(w1, x2, x3) - 8.0f * bsum.y, acc[r]);
-        }
-    }
-    if ((nb & 1) && lane == 0) {  // odd trailing block
-        const int j = nb - 1;
-        const int4 *xb = reinterpret_cast<const int4 *>(xrow) + j * 2;
-        const float sx1 = xsr[j], bs1 = xbr[j];
-        #pragma unroll
-        for (int r = 0; r < 4; r++)
-            acc[r] = fmaf(__half2float(srow[r][j]) * sx1,
-                          (float)q40_block_dot(wrow[r][j], xb[0], xb[1]) - 8.0f * bs1,
-                          acc[r]);
-    }
+    float acc[4] = {};
+    q40_q80_rows_dot<4>(wrow, srow, xq + (int64_t)br * n, xs + (int64_t)br * nb,
+                        xbs + (int64_t)br * nb, n, lane, WAVE, acc);
     #pragma unroll
     for (int r = 0; r < 4; r++) acc[r] = wave_reduce_sum(acc[r]);
     __shared__ float sv[32];
@@ -649,13 +593,13 @@ __global__ __launch_bounds__(1024) void k_q40_gemv_grouped_swiglu(
     }
     __syncthreads();
     if (threadIdx.x < 32) {
+        // ff % 32 == 0 (checked by the bindings), so a slot's ff codes are
+        // ff / QB whole blocks: code index slot * ff + bx * QB = blk * QB
+        const int64_t blk = (int64_t)slot * (ff / QB) + blockIdx.x;
         const Q80Lane c = q80_quant_group32(sv[threadIdx.x]);
-        oq[((int64_t)slot * ff) + blockIdx.x * QB + threadIdx.x] = (int8_t)c.qf;
+        oq[blk * QB + threadIdx.x] = (int8_t)c.qf;
         const float bsum = group32_reduce_sum(c.qf);
-        if (threadIdx.x == 0) {
-            os[(int64_t)slot * (ff / QB) + blockIdx.x] = c.d;
-            obs[(int64_t)slot * (ff / QB) + blockIdx.x] = bsum;
-        }
+        if (threadIdx.x == 0) { os[blk] = c.d; obs[blk] = bsum; }
     }
 }
 
@@ -1060,29 +1004,40 @@ void q40_gemv_grouped(torch::Tensor qs, torch::Tensor scales, torch::Tensor xq,
     }
 }
 
+// one launch of k_q40_gemv_swiglu over `n_slots` expert slots of ff/32
+// blocks each; router == nullptr is the dense form
+static void swiglu_launch(torch::Tensor &qs, torch::Tensor &scales, torch::Tensor &xq,
+                          torch::Tensor &xs, torch::Tensor &xbs, int ff, int n,
+                          int64_t n_slots, const float *router, int n_experts,
+                          int64_t topk, torch::Tensor &oq, torch::Tensor &os,
+                          torch::Tensor &obs, bool gelu) {
+    TORCH_CHECK(ff % 32 == 0, "fused swiglu GEMV needs ff % 32 == 0");
+    TORCH_CHECK(xq.size(-1) == n, "x width mismatch");
+    auto launch = [&](auto k) {
+        hipLaunchKernelGGL(k, dim3(ff / 32, n_slots), dim3(16 * WAVE), 0, cur_stream(),
+                           qs.data_ptr<uint8_t>(),
+                           reinterpret_cast<const __half *>(scales.data_ptr<at::Half>()),
+                           xq.data_ptr<int8_t>(), xs.data_ptr<float>(),
+                           xbs.data_ptr<float>(), ff, n, router, n_experts,
+                           (int)topk, oq.data_ptr<int8_t>(), os.data_ptr<float>(),
+                           obs.data_ptr<float>());
+    };
+    if (router == nullptr) {
+        if (gelu) launch(k_q40_gemv_swiglu<true, false>);
+        else launch(k_q40_gemv_swiglu<false, false>);
+    } else {
+        if (gelu) launch(k_q40_gemv_swiglu<true, true>);
+        else launch(k_q40_gemv_swiglu<false, true>);
+    }
+}
+
 void q40_gemv_swiglu(torch::Tensor qs, torch::Tensor scales, torch::Tensor xq,
                      torch::Tensor xs, torch::Tensor xbs, torch::Tensor oq,
                      torch::Tensor os, torch::Tensor obs, bool gelu = false) {
     // B=1 decode FFN: W1|W3 GEMV + SwiGLU + Q80 emit, one launch
     CHECK_CUDA(qs); CHECK_CONT(qs); CHECK_CONT(xq);
-    const int d = qs.size(0);
-    const int ff = d / 2;
-    const int n = qs.size(1) * 2;
-    TORCH_CHECK(ff % 32 == 0, "fused swiglu GEMV needs ff % 32 == 0");
-    TORCH_CHECK(xq.size(-1) == n, "x width mismatch");
-    const dim3 grid(ff / 32);
-    const dim3 block(16 * WAVE);
-    auto launch = [&](auto k) {
-        hipLaunchKernelGGL(k, grid, block, 0, cur_stream(),
-                           qs.data_ptr<uint8_t>(),
-                           reinterpret_cast<const __half *>(scales.data_ptr<at::Half>()),
-                           xq.data_ptr<int8_t>(), xs.data_ptr<float>(),
-                           xbs.data_ptr<float>(), ff, n,
-                           oq.data_ptr<int8_t>(), os.data_ptr<float>(),
-                           obs.data_ptr<float>());
-    };
-    if (gelu) launch(k_q40_gemv_swiglu<true>);
-    else launch(k_q40_gemv_swiglu<false>);
+    swiglu_launch(qs, scales, xq, xs, xbs, (int)qs.size(0) / 2, (int)qs.size(1) * 2,
+                  1, nullptr, 0, 0, oq, os, obs, gelu);
 }
 
 void q40_gemv_grouped_swiglu(torch::Tensor qs, torch::Tensor scales,
@@ -1096,22 +1051,10 @@ void q40_gemv_grouped_swiglu(torch::Tensor qs, torch::Tensor scales,
     // [n_slots, ff] Q80 triple.
     CHECK_CUDA(qs); CHECK_CONT(qs); CHECK_CONT(xq);
     const int ff = (int)qs.size(1) / 2;
-    const int n = (int)qs.size(2) * 2;
     TORCH_CHECK(ff % 32 == 0, "fused grouped swiglu needs ff % 32 == 0");
-    const dim3 grid(ff / 32, n_slots);
-    const dim3 block(16 * WAVE);
-    auto launch = [&](auto k) {
-        hipLaunchKernelGGL(k, grid, block, 0, cur_stream(),
-                           qs.data_ptr<uint8_t>(),
-                           reinterpret_cast<const __half *>(scales.data_ptr<at::Half>()),
-                           xq.data_ptr<int8_t>(), xs.data_ptr<float>(),
-                           xbs.data_ptr<float>(), ff, n,
-                           router.data_ptr<float>(), (int)router.size(-1),
-                           (int)topk, oq.data_ptr<int8_t>(),
-                           os.data_ptr<float>(), obs.data_ptr<float>());
-    };
-    if (gelu) launch(k_q40_gemv_grouped_swiglu<true>);
-    else launch(k_q40_gemv_grouped_swiglu<false>);
+    swiglu_launch(qs, scales, xq, xs, xbs, ff, (int)qs.size(2) * 2, n_slots,
+                  router.data_ptr<float>(), (int)router.size(-1), topk,
+                  oq, os, obs, gelu);
 }
 
 void register_gemv(py::module &m) {
