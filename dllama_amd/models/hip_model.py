@@ -145,6 +145,11 @@ class KVAddr:
         self.where = where
         self.attn_scratch = attn_scratch
         self.row_table = bool(suffix)  # a row step, not pos..pos+B-1
+        # the tiled MFMA chunk attention (set_chunk_attn): its binding, and
+        # for a row step that takes it the run table (runs, n_runs), staged
+        # with the row table; None = the step launches what it always did
+        self.attn_chunk = "attn_chunk" + suffix
+        self.chunk = None
 
 
 class HipTransformer:
@@ -264,6 +269,12 @@ class HipTransformer:
         # row steps (forward_rows) take the tier on request: set_wide_rows,
         # which BatchEngine calls, or DLLAMA_ATTN_WIDE_ROWS=1
         self.wide_rows = flag("DLLAMA_ATTN_WIDE_ROWS", "0")
+        # prompt chunks on the matrix cores: steps with a run of at least
+        # chunk_min_rows rows of one sequence take k_attn_chunk (K/V read
+        # once per chunk) instead of k_attn_split; f16 unpaged caches only.
+        # Off by default (docs/DESIGN.md §10); set_chunk_attn on a live model
+        self.chunk_attn = flag("DLLAMA_ATTN_CHUNK", "0")
+        self.chunk_min_rows = 8  # where the matmuls switch to the GEMM
         # the S in force above the wide tier, put back when a step leaves it
         self._splits_above = self.attn_splits if self.attn_splits != 1 else 8
         # measured-slower fusions kept for shape experiments (profiles r02):
@@ -590,12 +601,40 @@ class HipTransformer:
         cache into zbuf[:B]; emit_q80 also writes the Q80 triple zq that the
         wo matmul consumes."""
         c = self.cfg
+        chunk = self._chunk_step(B, addr)
+        if chunk is not None:
+            getattr(self.k, addr.attn_chunk)(
+                self.qkv_out, self.qkv_ld, self.k_cache[l], self.v_cache[l],
+                self.zbuf[:B], *addr.where, *chunk, B, c.n_heads0, self.kv_mul,
+                c.head_dim, self.attn_splits, self.attn_ml, self.attn_o,
+                *(self.zq.triple() if emit_q80 else ()))
+            return
         getattr(self.k, addr.attn)(
             self.qkv_out, self.qkv_ld, self.k_cache[l], self.v_cache[l],
             self.zbuf[:B], *addr.where, B, c.n_heads0, self.kv_mul,
             c.head_dim, self.attn_splits, self.attn_ml, self.attn_o,
             *addr.attn_scratch, *(self.zq.triple() if emit_q80 else ()),
             **self._kv_scales(l))
+
+    def _chunk_step(self, B: int, addr: KVAddr):
+        """The chunk attention's extra arguments if this step takes it, else
+        None: the option is on, the cache is f16 and unpaged, head_dim has an
+        instantiation, and the step has a run of chunk_min_rows rows (a
+        single-sequence step is one run of B rows; a row step's runs were
+        staged with its table)."""
+        if not (self.chunk_attn and self.kv_dtype == "f16"
+                and self.page_map is None and self.cfg.head_dim in (64, 128)):
+            return None
+        if addr.row_table:
+            return addr.chunk
+        return () if B >= self.chunk_min_rows else None
+
+    def set_chunk_attn(self, on: bool = True):
+        """Prompt-chunk steps take the tiled MFMA attention (or stop taking
+        it). Drops the captured graphs: a prefill graph holds one kernel or
+        the other."""
+        self.chunk_attn = bool(on)
+        self.graphs.clear()
 
     def _swiglu_q80(self, out13, rows: int, qb: QuantBuf, *act):
         """act(w1 x) * (w3 x) over the fused W1|W3 output -> Q80 triple."""
@@ -1224,16 +1263,18 @@ class HipTransformer:
     def _rows_buffers(self):
         """What the host sends per ragged step, in one allocation so a
         single small copy stages it: int64 words [tokens NB | per-row sampler
-        f64 {coin, temperature, topp, unused} 4*NB | row table int32 [NB, 2]].
-        The table is last: a step whose table the device already holds (a
-        replayed graph advanced it) copies the prefix only. Built on first
-        use, with its pinned host twin."""
+        f64 {coin, temperature, topp, unused} 4*NB | row table int32 [NB, 2]
+        | run table int32 [NB, 2]]. The tables are last: a step whose table
+        the device already holds (a replayed graph advanced it) copies the
+        prefix only, and the run table travels only with the chunk attention
+        on. Built on first use, with its pinned host twin."""
         if self._rows_io is None:
             NB, dev = self.n_batches, self.device
-            self._rows_io = io = torch.zeros(6 * NB, dtype=torch.int64, device=dev)
+            self._rows_io = io = torch.zeros(7 * NB, dtype=torch.int64, device=dev)
             self.row_tokens = io[:NB]
             self.row_params = io[NB:5 * NB].view(torch.float64).view(NB, 4)
-            self.rows = io[5 * NB:].view(torch.int32).view(NB, 2)
+            self.rows = io[5 * NB:6 * NB].view(torch.int32).view(NB, 2)
+            self.runs = io[6 * NB:].view(torch.int32).view(NB, 2)
             if self.page_map is not None:
                 self.row_addr = KVAddr("_paged", self.rows, self.page_table,
                                        self.page_size)
@@ -1244,7 +1285,7 @@ class HipTransformer:
             self._rows_out = torch.zeros(NB * LP_WORDS, dtype=torch.int64,
                                          device=dev)
             self.rows_sample_out = self._rows_out[:2 * NB].view(NB, 2)
-            self._rows_host = torch.zeros(6 * NB, dtype=torch.int64)
+            self._rows_host = torch.zeros(7 * NB, dtype=torch.int64)
             if dev.type == "cuda":
                 self._rows_host = self._rows_host.pin_memory()
             self._rows_copied = None  # event: the last staging copy is done
@@ -1270,7 +1311,7 @@ class HipTransformer:
     def _stage_rows(self, tokens, slots, positions, params=None):
         """Validate a ragged step and copy it to the device; returns
         (B, table, decode_only). params: per-row (coin, temperature, topp)."""
-        from .rows import check_rows, is_decode_step
+        from .rows import check_rows, is_decode_step, row_runs
         c, NB = self.cfg, self.n_batches
         tokens, slots, positions = check_rows(
             tokens, slots, positions, self.n_slots, c.seq_len, NB)
@@ -1291,13 +1332,27 @@ class HipTransformer:
         hp.zero_()  # temperature 0: a row nobody samples is an argmax
         if params is not None:
             hp[:B, :3] = torch.tensor(params, dtype=torch.float64)
+        # the runs follow from the slots: a step takes the chunk attention
+        # when its longest run has chunk_min_rows rows (never a decode step)
+        runs = None
+        if self.chunk_attn and self.page_map is None:
+            runs = row_runs(slots)
+            if max(n for _, n in runs) < self.chunk_min_rows:
+                runs = None
         words = 5 * NB
-        if self._rows_dev[:B] != table:
-            ht = host[5 * NB:].view(torch.int32).view(NB, 2)
+        if runs is not None or self._rows_dev[:B] != table:
+            ht = host[5 * NB:6 * NB].view(torch.int32).view(NB, 2)
             ht.zero_()
             ht[:B] = torch.tensor(table, dtype=torch.int32)
             words = 6 * NB
             self._rows_dev = list(table)
+        self.row_addr.chunk = None
+        if runs is not None:  # the run table travels behind the row table
+            hr = host[6 * NB:].view(torch.int32).view(NB, 2)
+            hr.zero_()
+            hr[:len(runs)] = torch.tensor(runs, dtype=torch.int32)
+            words = 7 * NB
+            self.row_addr.chunk = (self.runs, len(runs))
         self._rows_io[:words].copy_(host[:words], non_blocking=True)
         if self.device.type == "cuda":
             self._rows_copied = torch.cuda.Event()

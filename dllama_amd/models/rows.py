@@ -135,6 +135,22 @@ class PageMap:
                     f"which {self.users[page]} table entries share")
 
 
+RUN_ROWS = 32  # rows per run: the chunk attention's query tile
+
+
+def row_runs(slots: list[int]) -> list[tuple[int, int]]:
+    """The runs of a validated step as (first batch row, row count): a run
+    is a maximal stretch of consecutive batch rows with the same slot, cut
+    at RUN_ROWS rows. The chunk attention serves a run per workgroup."""
+    runs: list[tuple[int, int]] = []
+    for b, s in enumerate(slots):
+        if runs and slots[runs[-1][0]] == s and runs[-1][1] < RUN_ROWS:
+            runs[-1] = (runs[-1][0], runs[-1][1] + 1)
+        else:
+            runs.append((b, 1))
+    return runs
+
+
 def is_decode_step(slots: list[int]) -> bool:
     """Every row belongs to another sequence: one decode row each."""
     return len(set(slots)) == len(slots)

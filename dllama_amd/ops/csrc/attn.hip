@@ -729,6 +729,263 @@ __global__ void k_attn_combine(const float *__restrict__ ml_scratch,
     }
 }
 
+// ------------------------------------------------- tiled MFMA chunk attention
+// The prompt-chunk producer of the split scratch: the rows of a chunk differ
+// only in their causal mask, so one workgroup serves a whole run (<= 32
+// consecutive batch rows of one sequence) for all kv_mul query heads of a KV
+// head, and every K/V tile is read from the cache once per workgroup instead
+// of once per (head, row). Grid (n_kv_heads0, n_runs, S), 4 waves; wave w
+// owns query heads w, w+4, .. of the KV head (one pass over the timesteps
+// per group of 4 heads). Split sp walks the 32-timestep tiles sp, sp+S, ..
+// below the run's longest row; the grid does not depend on positions.
+//
+// Layouts (v_mfma_f32_32x32x16_f16, verified by tools/mfma_f16_probe.hip):
+// A[m][k] and B[k][n] hold k = 8*(lane>>5)+j in half j of lane (m or n)+32*hi;
+// C[m][n] holds n = lane&31, m = (r&3) + 8*(r>>2) + 4*(lane>>5) in register r.
+// Scores are computed transposed, S^T = K Q^T (m = timestep, n = query row):
+// a lane then holds 16 scores of ONE query row, so the online softmax is
+// lane-local but for one exchange with lane^32, and registers 8c..8c+7 of
+// the accumulator, rounded to f16, are directly the B operand of
+// O^T += V^T P^T over timesteps t = 16c + 8*(j>>2) + 4*hi + (j&3). The A
+// operand V^T gathers the same timesteps (k is only summed over): V is
+// transposed on its way into LDS, so that gather is two 8-byte LDS reads.
+// O^T again holds the lane's query row: m, l and the rescale stay per lane.
+//
+// Rounding points: q*scale (f32) -> f16 once, P -> f16 per tile; scores, m,
+// l and O accumulate in f32.
+typedef _Float16 v8h_t __attribute__((ext_vector_type(8)));
+typedef _Float16 v4h_t __attribute__((ext_vector_type(4)));
+typedef float v16f_t __attribute__((ext_vector_type(16)));
+
+// The kernel's independent f32 multiplies and fmas (the accumulator rescale,
+// the q scaling, the softmax exponents), spelled as the scalar-per-lane
+// instruction: the compiler would pair them into packed f32 VALU ops, which
+// this kernel keeps out (checked in its disassembly: no v_pk_*_f32).
+__device__ __forceinline__ float mul_f32(float a, float b) {
+    float r;
+    asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ float fma_f32(float a, float b, float c) {
+    float r;
+    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+
+constexpr int CHUNK_T = 32;     // timesteps per tile = MFMA M of the scores
+constexpr int CHUNK_ROWS = 32;  // query rows per run = MFMA N
+constexpr int CHUNK_NW = 4;     // waves per workgroup
+
+template <int VEC, typename ROWS>
+__global__ void __launch_bounds__(CHUNK_NW * WAVE, 2)
+k_attn_chunk(const float *__restrict__ q, int q_ld,
+             const __half *__restrict__ kc_all,
+             const __half *__restrict__ vc_all,
+             const ROWS rows, const int *__restrict__ runs, int batch,
+             int n_heads0, int kv_mul, int kv_dim0, float scale,
+             float *__restrict__ ml_scratch, float *__restrict__ o_scratch) {
+    constexpr int hd = VEC * WAVE;
+    constexpr int KLD = hd + 8;       // halves per K row: 16-byte rows, 4-bank skew
+    constexpr int VLD = CHUNK_T + 4;  // halves per V^T row (one d): 8-byte rows
+    constexpr int DCH = hd / 8;       // 16-byte chunks per cache row of the head
+    constexpr int NLD = CHUNK_T * DCH / (CHUNK_NW * WAVE);  // chunks per thread
+    static_assert(NLD * CHUNK_NW * WAVE == CHUNK_T * DCH, "tile / threads");
+    __shared__ __attribute__((aligned(16))) _Float16 sk[2][CHUNK_T * KLD];
+    __shared__ __attribute__((aligned(16))) _Float16 sv[2][hd * VLD];
+
+    const int kvh = blockIdx.x;
+    const int sp = blockIdx.z;
+    const int S = gridDim.z;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+    const int lane = threadIdx.x % WAVE;
+    const int row = lane & 31;  // query row of the run (B / C operand column)
+    const int hi = lane >> 5;
+
+    // the run: SeqRows = the whole batch; a table run is clamped to the batch
+    // and to the tile, so a bad table cannot send a load or store astray
+    int b0 = 0, n = batch;
+    if constexpr (!std::is_same_v<ROWS, SeqRows>) {
+        b0 = min(max(runs[2 * blockIdx.y], 0), batch - 1);
+        n = min(runs[2 * blockIdx.y + 1], batch - b0);
+    }
+    n = min(n, CHUNK_ROWS);
+    const bool real = row < n;  // else a padding row: q = 0, never written
+    const int b = b0 + (real ? row : 0);
+    int plen = real ? rows.position(b) + 1 : 0;
+    int maxlen = plen, minlen;
+    #pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        maxlen = max(maxlen, __shfl_xor(maxlen, off, WAVE));
+    maxlen = __builtin_amdgcn_readfirstlane(maxlen);
+    if (!real) plen = maxlen;  // a padding row masks nothing
+    minlen = plen;
+    #pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        minlen = min(minlen, __shfl_xor(minlen, off, WAVE));
+    minlen = __builtin_amdgcn_readfirstlane(minlen);
+
+    const __half *kc = kc_all + rows.cache_base(b0) * kv_dim0 + kvh * hd;
+    const __half *vc = vc_all + rows.cache_base(b0) * kv_dim0 + kvh * hd;
+
+    // staging: thread holds NLD 16-byte chunks of the K tile and of the V
+    // tile in registers between their global load and their LDS store. A
+    // timestep at or past maxlen (last tile only) re-reads row maxlen-1: a
+    // valid row, masked below.
+    v8h_t kreg[NLD], vreg[NLD];
+    auto tile_load = [&](int tile) {
+        #pragma unroll
+        for (int it = 0; it < NLD; it++) {
+            const int idx = threadIdx.x + it * CHUNK_NW * WAVE;
+            const int t = min(tile * CHUNK_T + idx / DCH, maxlen - 1);
+            const int64_t off = (int64_t)t * kv_dim0 + (idx % DCH) * 8;
+            kreg[it] = *reinterpret_cast<const v8h_t *>(kc + off);
+            vreg[it] = *reinterpret_cast<const v8h_t *>(vc + off);
+        }
+    };
+    auto tile_store = [&](int buf) {
+        #pragma unroll
+        for (int it = 0; it < NLD; it++) {
+            const int idx = threadIdx.x + it * CHUNK_NW * WAVE;
+            const int t = idx / DCH, d = (idx % DCH) * 8;
+            *reinterpret_cast<v8h_t *>(&sk[buf][t * KLD + d]) = kreg[it];
+            #pragma unroll
+            for (int i = 0; i < 8; i++) sv[buf][(d + i) * VLD + t] = vreg[it][i];
+        }
+    };
+
+    for (int hg = 0; hg < kv_mul; hg += CHUNK_NW) {
+        const bool active = hg + wave < kv_mul;  // wave-uniform
+        const int h0 = kvh * kv_mul + hg + wave;
+
+        // q * scale in f32, rounded to f16 once: the B operand for the pass
+        v8h_t qf[hd / 16];
+        #pragma unroll
+        for (int kb = 0; kb < hd / 16; kb++) {
+            float4 x0 = {0.f, 0.f, 0.f, 0.f}, x1 = x0;
+            if (active && real) {
+                const float *qp = q + (int64_t)b * q_ld + h0 * hd + kb * 16 + hi * 8;
+                x0 = *reinterpret_cast<const float4 *>(qp);
+                x1 = *reinterpret_cast<const float4 *>(qp + 4);
+            }
+            qf[kb] = v8h_t{
+                (_Float16)mul_f32(x0.x, scale), (_Float16)mul_f32(x0.y, scale),
+                (_Float16)mul_f32(x0.z, scale), (_Float16)mul_f32(x0.w, scale),
+                (_Float16)mul_f32(x1.x, scale), (_Float16)mul_f32(x1.y, scale),
+                (_Float16)mul_f32(x1.z, scale), (_Float16)mul_f32(x1.w, scale)};
+        }
+
+        v16f_t o[hd / 32];
+        #pragma unroll
+        for (int mb = 0; mb < hd / 32; mb++)
+            #pragma unroll
+            for (int r = 0; r < 16; r++) o[mb][r] = 0.0f;
+        // this lane's half of the row's l (its 16 timesteps per tile); m is
+        // the row's, equal in lane and lane^32
+        float m = -1e30f, l = 0.0f;
+
+        // double-buffered: tile i+S is in flight from the cache while tile i
+        // is multiplied; one barrier per tile (the buffer stored to at the
+        // end of an iteration was last read before the previous barrier)
+        int tile = sp, buf = 0;
+        if (tile * CHUNK_T < maxlen) {
+            tile_load(tile);
+            tile_store(0);
+        }
+        __syncthreads();
+        for (; tile * CHUNK_T < maxlen; tile += S, buf ^= 1) {
+            const bool more = (tile + S) * CHUNK_T < maxlen;
+            if (more) tile_load(tile + S);
+            if (active) {
+                const int t0 = tile * CHUNK_T;
+                v16f_t s;
+                #pragma unroll
+                for (int r = 0; r < 16; r++) s[r] = 0.0f;
+                #pragma unroll
+                for (int kb = 0; kb < hd / 16; kb++) {
+                    const v8h_t kf = *reinterpret_cast<const v8h_t *>(
+                        &sk[buf][row * KLD + kb * 16 + hi * 8]);
+                    s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kb], s,
+                                                               0, 0, 0);
+                }
+                // only a tile that reaches past the run's shortest row masks
+                const bool straddle = t0 + CHUNK_T > minlen;
+                float mx = -1e30f;
+                #pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int t = t0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    if (straddle && t >= plen) s[r] = -1e30f;
+                    mx = fmaxf(mx, s[r]);
+                }
+                mx = fmaxf(mx, __shfl_xor(mx, 32, WAVE));
+                const float mn = fmaxf(m, mx);
+                // exp(x - mn) as exp2(x * log2(e) - mn * log2(e)), one fma
+                constexpr float LOG2E = 1.4426950408889634f;
+                const float nmn = -mn * LOG2E;
+                // m = -1e30 (nothing valid yet): l and o are 0, any finite
+                // f does; the fma's rounding of 1e30-sized terms would not be
+                const float f = m > -1e30f
+                    ? __builtin_amdgcn_exp2f(fma_f32(m, LOG2E, nmn)) : 0.0f;
+                float p[16], ls = 0.0f;
+                #pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int t = t0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    // a masked weight is 0 by name: a row with nothing valid
+                    // yet has mn = -1e30, where exp(s - mn) would be 1
+                    p[r] = (straddle && t >= plen) ? 0.0f
+                        : __builtin_amdgcn_exp2f(fma_f32(s[r], LOG2E, nmn));
+                    ls += p[r];
+                }
+                l = l * f + ls;
+                m = mn;
+                v8h_t pf[2];
+                #pragma unroll
+                for (int c = 0; c < 2; c++)
+                    #pragma unroll
+                    for (int j = 0; j < 8; j++) pf[c][j] = (_Float16)p[8 * c + j];
+                #pragma unroll
+                for (int mb = 0; mb < hd / 32; mb++) {
+                    #pragma unroll
+                    for (int r = 0; r < 16; r++) o[mb][r] = mul_f32(o[mb][r], f);
+                    #pragma unroll
+                    for (int c = 0; c < 2; c++) {
+                        const _Float16 *vp =
+                            &sv[buf][(mb * 32 + row) * VLD + 16 * c + 4 * hi];
+                        const v4h_t v0 = *reinterpret_cast<const v4h_t *>(vp);
+                        const v4h_t v1 = *reinterpret_cast<const v4h_t *>(vp + 8);
+                        const v8h_t vf = __builtin_shufflevector(
+                            v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
+                        o[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(
+                            vf, pf[c], o[mb], 0, 0, 0);
+                    }
+                }
+            }
+            if (more) tile_store(buf ^ 1);
+            __syncthreads();
+        }
+
+        if (active) {
+            l += __shfl_xor(l, 32, WAVE);
+            if (real) {
+                // a row with no timestep in this split leaves m = -1e30,
+                // l = 0, o = 0, as k_attn_split does
+                const int64_t slot = ((int64_t)b * n_heads0 + h0) * S + sp;
+                if (hi == 0) {
+                    ml_scratch[slot * 2] = m;
+                    ml_scratch[slot * 2 + 1] = l;
+                }
+                #pragma unroll
+                for (int mb = 0; mb < hd / 32; mb++)
+                    #pragma unroll
+                    for (int g = 0; g < 4; g++)
+                        *reinterpret_cast<float4 *>(
+                            o_scratch + slot * hd + mb * 32 + 8 * g + 4 * hi) =
+                            float4{o[mb][4 * g], o[mb][4 * g + 1],
+                                   o[mb][4 * g + 2], o[mb][4 * g + 3]};
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------ rope
 // style 0 = llama interleaved pairs (reference ropeLlama_F32,
 // nn-cpu-ops.cpp:843-863), style 1 = falcon/neox half-rotated
@@ -1153,6 +1410,22 @@ static PagedRows paged_rows(const torch::Tensor &rows,
     return PagedRows{t.rows, page_table.data_ptr<int>(), shift};
 }
 
+// Stage 2 for every producer of the split scratch; zq selects the Q80 form.
+template <int V>
+static void combine_launch(torch::Tensor &ml_scratch, torch::Tensor &o_scratch,
+                           float *yp, int8_t *zqp, float *zsp, float *zbsp,
+                           int64_t batch, int64_t n_heads0, int64_t splits) {
+    auto combine = [&](auto quant_const) {
+        hipLaunchKernelGGL((k_attn_combine<V, decltype(quant_const)::value>),
+                           dim3(n_heads0, batch), dim3(V * WAVE), 0,
+                           cur_stream(), ml_scratch.data_ptr<float>(),
+                           o_scratch.data_ptr<float>(), yp, zqp, zsp, zbsp,
+                           (int)n_heads0, (int)splits);
+    };
+    if (zqp) combine(std::true_type{});
+    else combine(std::false_type{});
+}
+
 // The launches of attention, for any row addressing: the wide single kernel
 // when splits == 1 and the output is the Q80 triple, else split + combine.
 // The GQA-grouped experiment exists for the single-sequence form only.
@@ -1246,15 +1519,8 @@ static void attn_launch(torch::Tensor &q, int64_t q_ld, torch::Tensor &kc,
             }
         });
         if (wide) return;
-        auto combine = [&](auto quant_const) {
-            hipLaunchKernelGGL((k_attn_combine<V, decltype(quant_const)::value>),
-                               cgrid, dim3(V * WAVE), 0, cur_stream(),
-                               ml_scratch.data_ptr<float>(),
-                               o_scratch.data_ptr<float>(), yp, zqp, zsp, zbsp,
-                               (int)n_heads0, (int)splits);
-        };
-        if (quant) combine(std::true_type{});
-        else combine(std::false_type{});
+        combine_launch<V>(ml_scratch, o_scratch, yp, zqp, zsp, zbsp, batch,
+                          n_heads0, splits);
     });
 }
 
@@ -1306,6 +1572,107 @@ void attn_paged(torch::Tensor q, int64_t q_ld, torch::Tensor kc, torch::Tensor v
                 n_heads0, kv_mul, head_dim, splits, ml_scratch, o_scratch,
                 zq, zs, zbs,
                 k_scales, v_scales);
+}
+
+// Prompt-chunk attention: k_attn_chunk fills the split scratch, the combine
+// finishes as for k_attn_split. `runs` is null for the single sequence (the
+// batch is one run). What the host can see is checked here; the contents of
+// the row and run tables are the caller's (models/rows.py row_runs), and the
+// kernel clamps a run to the batch and to 32 rows.
+template <typename ROWS>
+static void attn_chunk_launch(const char *name, const char *other,
+                              torch::Tensor &q, int64_t q_ld, torch::Tensor &kc,
+                              torch::Tensor &vc, torch::Tensor &y, ROWS rows,
+                              const int *runs, int64_t n_runs, int64_t batch,
+                              int64_t n_heads0, int64_t kv_mul,
+                              int64_t head_dim, int64_t splits,
+                              torch::Tensor &ml_scratch,
+                              torch::Tensor &o_scratch, OptTensor &zq,
+                              OptTensor &zs, OptTensor &zbs,
+                              const OptTensor &k_scales,
+                              const OptTensor &v_scales) {
+    CHECK_CUDA(q);
+    TORCH_CHECK(kc.scalar_type() == at::kHalf && vc.scalar_type() == at::kHalf,
+                name, " serves a float16 KV cache only: use ", other,
+                " for a float32 or int8 (Q80) cache");
+    TORCH_CHECK(!k_scales.has_value() && !v_scales.has_value(), name,
+                " takes no k_scales / v_scales: use ", other,
+                " for a Q80 KV cache");
+    TORCH_CHECK(head_dim == 64 || head_dim == 128, name,
+                " serves head_dim 64 and 128 (got ", head_dim, "): use ", other);
+    TORCH_CHECK(batch >= 1 && n_runs >= 1 && batch <= n_runs * CHUNK_ROWS, name,
+                ": a run holds at most ", CHUNK_ROWS, " rows (", batch,
+                " rows in ", n_runs, " runs): cut it, or use ", other);
+    TORCH_CHECK(kv_mul >= 1 && n_heads0 % kv_mul == 0 && splits >= 1
+                && q_ld % 4 == 0 && kc.dim() == 2 && kc.is_contiguous()
+                && vc.is_contiguous() && kc.sizes() == vc.sizes()
+                && kc.size(1) == n_heads0 / kv_mul * head_dim,
+                name, ": contiguous caches [rows, n_kv_heads0 * head_dim], "
+                "n_heads0 a multiple of kv_mul, q_ld a multiple of 4");
+    const int64_t slots = batch * n_heads0 * splits;
+    TORCH_CHECK(ml_scratch.numel() >= slots * 2
+                && o_scratch.numel() >= slots * head_dim,
+                name, ": split scratch too small for ", slots, " partials");
+    const bool quant = zq.has_value();
+    float *yp = quant ? nullptr : y.data_ptr<float>();
+    int8_t *zqp = quant ? zq->data_ptr<int8_t>() : nullptr;
+    float *zsp = quant ? zs->data_ptr<float>() : nullptr;
+    float *zbsp = quant ? zbs->data_ptr<float>() : nullptr;
+    const dim3 grid(n_heads0 / kv_mul, n_runs, splits);
+    with_head_vec(head_dim, [&](auto vec_const) {
+        constexpr int V = decltype(vec_const)::value;
+        hipLaunchKernelGGL((k_attn_chunk<V, ROWS>), grid,
+                           dim3(CHUNK_NW * WAVE), 0, cur_stream(),
+                           q.data_ptr<float>(), (int)q_ld,
+                           reinterpret_cast<const __half *>(
+                               kc.data_ptr<at::Half>()),
+                           reinterpret_cast<const __half *>(
+                               vc.data_ptr<at::Half>()),
+                           rows, runs, (int)batch, (int)n_heads0, (int)kv_mul,
+                           (int)kc.size(1), 1.0f / sqrtf((float)head_dim),
+                           ml_scratch.data_ptr<float>(),
+                           o_scratch.data_ptr<float>());
+        combine_launch<V>(ml_scratch, o_scratch, yp, zqp, zsp, zbsp, batch,
+                          n_heads0, splits);
+    });
+}
+
+// attn for a prompt chunk of one sequence: rows 0..batch-1 are one run.
+void attn_chunk(torch::Tensor q, int64_t q_ld, torch::Tensor kc,
+                torch::Tensor vc, torch::Tensor y, torch::Tensor pos,
+                int64_t batch, int64_t n_heads0, int64_t kv_mul,
+                int64_t head_dim, int64_t splits, torch::Tensor ml_scratch,
+                torch::Tensor o_scratch, OptTensor zq = c10::nullopt,
+                OptTensor zs = c10::nullopt, OptTensor zbs = c10::nullopt,
+                OptTensor k_scales = c10::nullopt,
+                OptTensor v_scales = c10::nullopt) {
+    attn_chunk_launch("attn_chunk", "attn", q, q_ld, kc, vc, y,
+                      SeqRows{pos.data_ptr<int>()}, nullptr, 1, batch, n_heads0,
+                      kv_mul, head_dim, splits, ml_scratch, o_scratch, zq, zs,
+                      zbs, k_scales, v_scales);
+}
+
+// attn_rows with the rows grouped into runs: int32 [n_runs, 2] = {first
+// batch row, row count}, each run consecutive rows of one sequence.
+void attn_chunk_rows(torch::Tensor q, int64_t q_ld, torch::Tensor kc,
+                     torch::Tensor vc, torch::Tensor y, torch::Tensor rows,
+                     torch::Tensor runs, int64_t n_runs, int64_t batch,
+                     int64_t n_heads0, int64_t kv_mul, int64_t head_dim,
+                     int64_t splits, torch::Tensor ml_scratch,
+                     torch::Tensor o_scratch, OptTensor zq = c10::nullopt,
+                     OptTensor zs = c10::nullopt, OptTensor zbs = c10::nullopt,
+                     OptTensor k_scales = c10::nullopt,
+                     OptTensor v_scales = c10::nullopt) {
+    TORCH_CHECK(runs.is_cuda() && runs.scalar_type() == at::kInt
+                && runs.dim() == 2 && runs.size(1) == 2 && runs.is_contiguous()
+                && n_runs >= 1 && runs.size(0) >= n_runs
+                && runs.device() == kc.device(),
+                "run table must be a contiguous int32 [>= n_runs, 2] on the "
+                "cache's device (or use attn_rows)");
+    attn_chunk_launch("attn_chunk_rows", "attn_rows", q, q_ld, kc, vc, y,
+                      table_rows(rows, batch), runs.data_ptr<int>(), n_runs,
+                      batch, n_heads0, kv_mul, head_dim, splits, ml_scratch,
+                      o_scratch, zq, zs, zbs, k_scales, v_scales);
 }
 
 // The Q80 write kernel for either launcher below; mode as k_rope_kv_q80's
@@ -1509,6 +1876,20 @@ void register_attn(py::module &m) {
     m.def("attn_paged", &attn_paged, py::arg("q"), py::arg("q_ld"),
           py::arg("kc"), py::arg("vc"), py::arg("y"), py::arg("rows"),
           py::arg("page_table"), py::arg("page_size"), py::arg("batch"),
+          py::arg("n_heads0"), py::arg("kv_mul"), py::arg("head_dim"),
+          py::arg("splits"), py::arg("ml_scratch"), py::arg("o_scratch"),
+          py::arg("zq") = py::none(), py::arg("zs") = py::none(),
+          py::arg("zbs") = py::none(), KV_SCALE_ARGS);
+    m.def("attn_chunk", &attn_chunk, py::arg("q"), py::arg("q_ld"),
+          py::arg("kc"), py::arg("vc"), py::arg("y"), py::arg("pos"),
+          py::arg("batch"), py::arg("n_heads0"), py::arg("kv_mul"),
+          py::arg("head_dim"), py::arg("splits"), py::arg("ml_scratch"),
+          py::arg("o_scratch"), py::arg("zq") = py::none(),
+          py::arg("zs") = py::none(), py::arg("zbs") = py::none(),
+          KV_SCALE_ARGS);
+    m.def("attn_chunk_rows", &attn_chunk_rows, py::arg("q"), py::arg("q_ld"),
+          py::arg("kc"), py::arg("vc"), py::arg("y"), py::arg("rows"),
+          py::arg("runs"), py::arg("n_runs"), py::arg("batch"),
           py::arg("n_heads0"), py::arg("kv_mul"), py::arg("head_dim"),
           py::arg("splits"), py::arg("ml_scratch"), py::arg("o_scratch"),
           py::arg("zq") = py::none(), py::arg("zs") = py::none(),

@@ -61,6 +61,50 @@ def attn_ab(positions=(32, 128, 250, 500, 1000), rounds=5):
             for name, t in times.items()))
 
 
+def chunk_ab(positions=(512, 2048, 4096, 8192), batches=(32,), rounds=3,
+             splits=(8, 16, 32, 64)):
+    """Prompt-chunk attention alone in an isolated hipGraph at the 8B shape
+    (32 heads, kv_mul 4, hd 128, f16 KV, Q80 output), B rows at first position
+    p: k_attn_split + combine against k_attn_chunk + combine at every S,
+    interleaved over `rounds`; median us per call, and the largest |code|
+    difference between the two Q80 outputs at the first S.
+
+      python tools/kernel_bench.py chunk            B = 32
+      python tools/kernel_bench.py chunk-rows       B = 4, 8, 16, 32 (threshold)"""
+    H0, hd, kvd, kv_mul = 32, 128, 1024, 4
+    seq = max(positions) + 64
+    kc = (torch.randn(seq, kvd, device=dev, generator=g) * 0.3).half()
+    vc = torch.randn(seq, kvd, device=dev, generator=g).half()
+    print("\n-- chunk attention, isolated graph, 8B shape, f16 KV, Q80 out "
+          "(median us per call: split / chunk) --")
+    for B in batches:
+        qv = torch.randn(B, H0 * hd, device=dev, generator=g)
+        y = torch.zeros(B, H0 * hd, device=dev)
+        cnt = torch.zeros(B * H0, dtype=torch.int32, device=dev)
+        z = [[torch.zeros(B, H0 * hd, dtype=torch.int8, device=dev),
+              torch.zeros(B, H0 * hd // 32, device=dev),
+              torch.zeros(B, H0 * hd // 32, device=dev)] for _ in range(2)]
+        for p in positions:
+            pos = torch.tensor([p], dtype=torch.int32, device=dev)
+            out = []
+            for S in splits:
+                ml = torch.zeros(B * H0 * S * 2, device=dev)
+                osc = torch.zeros(B * H0 * S * hd, device=dev)
+                split = lambda: k.attn(qv, H0 * hd, kc, vc, y, pos, B, H0,
+                                       kv_mul, hd, S, ml, osc, cnt, *z[0])
+                chunk = lambda: k.attn_chunk(qv, H0 * hd, kc, vc, y, pos, B,
+                                             H0, kv_mul, hd, S, ml, osc, *z[1])
+                t = {"split": [], "chunk": []}
+                for _ in range(rounds):
+                    t["split"].append(bench(split, n=16, reps=3))
+                    t["chunk"].append(bench(chunk, n=16, reps=3))
+                out.append(f"S={S}: {statistics.median(t['split']):7.1f} /"
+                           f" {statistics.median(t['chunk']):7.1f}")
+            diff = (z[0][0].int() - z[1][0].int()).abs().max().item()
+            print(f"B={B:2d} pos={p:5d}  " + "  ".join(out)
+                  + f"  max |dcode| {diff}")
+
+
 def resid_ab(rounds=5, forms=(16, 8, 4)):
     """q40_gemv_resid_q alone in an isolated hipGraph at the down-projection
     shapes (wo, w2) of the 1B, 3B, 8B and 70B presets, one column per
@@ -129,6 +173,12 @@ def resid_ab(rounds=5, forms=(16, 8, 4)):
 
 if sys.argv[1:] == ["attn"]:
     attn_ab()
+    sys.exit(0)
+if sys.argv[1:] == ["chunk"]:
+    chunk_ab()
+    sys.exit(0)
+if sys.argv[1:] == ["chunk-rows"]:
+    chunk_ab(positions=(512, 4096), batches=(4, 8, 16, 32), splits=(16, 32))
     sys.exit(0)
 if sys.argv[1:] == ["resid"]:
     resid_ab()

@@ -1,21 +1,44 @@
-"""Prefill throughput probe: 512-token prompt through the int8-MFMA GEMM path."""
-import sys, time, torch
-sys.path.insert(0, "/root/repo")
+"""Prefill throughput probe: prompts of 512, 2k and 8k tokens through the
+int8-MFMA GEMM path of a synthetic Llama-3.1-8B, in 32-token chunks, with the
+chunk attention (set_chunk_attn) off and on, alternating. Per length and
+setting: ms and tok/s of every repetition (each pays its own prefill-graph
+captures, which the switch drops: the same cost in both settings), and the
+tok/s of the last 512 tokens alone, where the context is longest.
+
+  python tools/prefill_probe.py [lengths...]      default 512 2048 8192"""
+import os, sys, time, torch
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from dllama_amd.model_file import preset_header
 from dllama_amd.models.config import ModelConfig
 from dllama_amd.models.hip_model import HipTransformer
 
-h = preset_header("llama-3.1-8b", seq_len=4096)
+lengths = [int(a) for a in sys.argv[1:]] or [512, 2048, 8192]
+h = preset_header("llama-3.1-8b", seq_len=max(lengths))
 cfg = ModelConfig.from_header(h)
 m = HipTransformer.synthetic(cfg)
-prompt = torch.randint(0, 128256, (512,))
-for rep in range(3):
+prompt = torch.randint(0, 128256, (max(lengths),))
+
+
+def prefill(n):
+    """(seconds for n tokens, seconds for the last 512 of them)."""
     m.pos.fill_(0)
-    torch.cuda.synchronize(); t0 = time.perf_counter()
-    for i in range(0, 512, 32):
-        m.skip_logits = i < 480
+    torch.cuda.synchronize(); t0 = t_tail = time.perf_counter()
+    for i in range(0, n, 32):
+        if i == n - 512:
+            torch.cuda.synchronize(); t_tail = time.perf_counter()
+        m.skip_logits = i < n - 32
         m.forward(prompt[i:i+32], torch.arange(i, i+32))
         m.skip_logits = False
     torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    print(f"prefill 512 tokens: {dt*1000:.1f} ms = {512/dt:.0f} tok/s")
+    t1 = time.perf_counter()
+    return t1 - t0, t1 - t_tail
+
+
+for n in lengths:
+    for rep in range(3):
+        for on in (False, True):
+            m.set_chunk_attn(on)
+            dt, tail = prefill(n)
+            print(f"prefill {n:5d} tokens, chunk attn {'on ' if on else 'off'}: "
+                  f"{dt*1000:8.1f} ms = {n/dt:6.0f} tok/s; last 512: "
+                  f"{512/tail:6.0f} tok/s", flush=True)
