@@ -271,9 +271,12 @@ class HipTransformer:
         self.wide_rows = flag("DLLAMA_ATTN_WIDE_ROWS", "0")
         # prompt chunks on the matrix cores: steps with a run of at least
         # chunk_min_rows rows of one sequence take k_attn_chunk (K/V read
-        # once per chunk) instead of k_attn_split; f16 unpaged caches only.
-        # Off by default (docs/DESIGN.md §10); set_chunk_attn on a live model
-        self.chunk_attn = flag("DLLAMA_ATTN_CHUNK", "0")
+        # once per chunk) instead of k_attn_split, paged or not. Level 1
+        # serves f16 caches; level 2 (chunk_attn_q80) Q80 caches as well,
+        # which adds a rounding point of its own. Off by default
+        # (docs/DESIGN.md §10); set_chunk_attn on a live model
+        self.chunk_attn = env.get("DLLAMA_ATTN_CHUNK", "0") in ("1", "2")
+        self.chunk_attn_q80 = env.get("DLLAMA_ATTN_CHUNK", "0") == "2"
         self.chunk_min_rows = 8  # where the matmuls switch to the GEMM
         # the S in force above the wide tier, put back when a step leaves it
         self._splits_above = self.attn_splits if self.attn_splits != 1 else 8
@@ -607,7 +610,8 @@ class HipTransformer:
                 self.qkv_out, self.qkv_ld, self.k_cache[l], self.v_cache[l],
                 self.zbuf[:B], *addr.where, *chunk, B, c.n_heads0, self.kv_mul,
                 c.head_dim, self.attn_splits, self.attn_ml, self.attn_o,
-                *(self.zq.triple() if emit_q80 else ()))
+                *(self.zq.triple() if emit_q80 else ()),
+                **self._kv_scales(l))
             return
         getattr(self.k, addr.attn)(
             self.qkv_out, self.qkv_ld, self.k_cache[l], self.v_cache[l],
@@ -618,22 +622,30 @@ class HipTransformer:
 
     def _chunk_step(self, B: int, addr: KVAddr):
         """The chunk attention's extra arguments if this step takes it, else
-        None: the option is on, the cache is f16 and unpaged, head_dim has an
-        instantiation, and the step has a run of chunk_min_rows rows (a
-        single-sequence step is one run of B rows; a row step's runs were
-        staged with its table)."""
-        if not (self.chunk_attn and self.kv_dtype == "f16"
-                and self.page_map is None and self.cfg.head_dim in (64, 128)):
+        None: the option is on, the cache is f16 (or Q80 at the option's
+        second level), head_dim has an instantiation, and the step has a run
+        of chunk_min_rows rows (a single-sequence step is one run of B rows;
+        a row step's runs were staged with its table)."""
+        if not self._chunk_served():
             return None
         if addr.row_table:
             return addr.chunk
         return () if B >= self.chunk_min_rows else None
 
-    def set_chunk_attn(self, on: bool = True):
+    def _chunk_served(self) -> bool:
+        """The option is on at a level that serves this model's cache."""
+        served = self.kv_dtype == "f16" or (
+            self.kv_dtype == "q80" and self.chunk_attn_q80)
+        return bool(self.chunk_attn and served
+                    and self.cfg.head_dim in (64, 128))
+
+    def set_chunk_attn(self, on: bool = True, q80: bool = False):
         """Prompt-chunk steps take the tiled MFMA attention (or stop taking
-        it). Drops the captured graphs: a prefill graph holds one kernel or
-        the other."""
+        it); q80=True extends it to a Q80 KV cache, which `on` alone leaves
+        on its old launches. Drops the captured graphs: a prefill graph holds
+        one kernel or the other."""
         self.chunk_attn = bool(on)
+        self.chunk_attn_q80 = bool(on) and bool(q80)
         self.graphs.clear()
 
     def _swiglu_q80(self, out13, rows: int, qb: QuantBuf, *act):
@@ -1335,7 +1347,7 @@ class HipTransformer:
         # the runs follow from the slots: a step takes the chunk attention
         # when its longest run has chunk_min_rows rows (never a decode step)
         runs = None
-        if self.chunk_attn and self.page_map is None:
+        if self._chunk_served():
             runs = row_runs(slots)
             if max(n for _, n in runs) < self.chunk_min_rows:
                 runs = None

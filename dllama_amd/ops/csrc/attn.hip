@@ -751,8 +751,15 @@ __global__ void k_attn_combine(const float *__restrict__ ml_scratch,
 // transposed on its way into LDS, so that gather is two 8-byte LDS reads.
 // O^T again holds the lane's query row: m, l and the rescale stay per lane.
 //
-// Rounding points: q*scale (f32) -> f16 once, P -> f16 per tile; scores, m,
-// l and O accumulate in f32.
+// Rounding points: q*scale (f32) -> f16 once, P -> f16 per tile, and K and V
+// of a Q80 cache: code * d rounded to f16; scores, m, l and O accumulate in
+// f32.
+//
+// Forms: KVT is the cache element (__half, or int8_t for the code planes of a
+// Q80 cache with ROWS = Q80Rows<..>), ROWS any of the three addressing
+// policies. They differ only in how a tile gets from the cache into LDS
+// (tile_load / tile_store below); LDS always holds f16 tiles and everything
+// after the barrier is shared code.
 typedef _Float16 v8h_t __attribute__((ext_vector_type(8)));
 typedef _Float16 v4h_t __attribute__((ext_vector_type(4)));
 typedef float v16f_t __attribute__((ext_vector_type(16)));
@@ -776,14 +783,28 @@ constexpr int CHUNK_T = 32;     // timesteps per tile = MFMA M of the scores
 constexpr int CHUNK_ROWS = 32;  // query rows per run = MFMA N
 constexpr int CHUNK_NW = 4;     // waves per workgroup
 
-template <int VEC, typename ROWS>
+// 8 consecutive Q80 codes (two dwords of a cache row) times their block's
+// scale, as f16: f16(code) is exact and the one f16 multiply rounds the exact
+// product code * d once, so this is f16(code * f32(d)).
+__device__ __forceinline__ v8h_t q80_codes_f16(int2 c, _Float16 d) {
+    v8h_t out;
+    #pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const int w = i < 4 ? c.x : c.y;
+        out[i] = (_Float16)(short)(int8_t)(w >> (8 * (i & 3)));
+    }
+    return out * d;
+}
+
+template <int VEC, typename KVT, typename ROWS>
 __global__ void __launch_bounds__(CHUNK_NW * WAVE, 2)
 k_attn_chunk(const float *__restrict__ q, int q_ld,
-             const __half *__restrict__ kc_all,
-             const __half *__restrict__ vc_all,
+             const KVT *__restrict__ kc_all,
+             const KVT *__restrict__ vc_all,
              const ROWS rows, const int *__restrict__ runs, int batch,
              int n_heads0, int kv_mul, int kv_dim0, float scale,
              float *__restrict__ ml_scratch, float *__restrict__ o_scratch) {
+    constexpr bool Q8 = kKVQ80<KVT>;
     constexpr int hd = VEC * WAVE;
     constexpr int KLD = hd + 8;       // halves per K row: 16-byte rows, 4-bank skew
     constexpr int VLD = CHUNK_T + 4;  // halves per V^T row (one d): 8-byte rows
@@ -804,7 +825,7 @@ k_attn_chunk(const float *__restrict__ q, int q_ld,
     // the run: SeqRows = the whole batch; a table run is clamped to the batch
     // and to the tile, so a bad table cannot send a load or store astray
     int b0 = 0, n = batch;
-    if constexpr (!std::is_same_v<ROWS, SeqRows>) {
+    if constexpr (!std::is_base_of_v<SeqRows, ROWS>) {
         b0 = min(max(runs[2 * blockIdx.y], 0), batch - 1);
         n = min(runs[2 * blockIdx.y + 1], batch - b0);
     }
@@ -824,22 +845,73 @@ k_attn_chunk(const float *__restrict__ q, int q_ld,
         minlen = min(minlen, __shfl_xor(minlen, off, WAVE));
     minlen = __builtin_amdgcn_readfirstlane(minlen);
 
-    const __half *kc = kc_all + rows.cache_base(b0) * kv_dim0 + kvh * hd;
-    const __half *vc = vc_all + rows.cache_base(b0) * kv_dim0 + kvh * hd;
+    const KVT *kc = kc_all + rows.cache_base(b0) * kv_dim0 + kvh * hd;
+    const KVT *vc = vc_all + rows.cache_base(b0) * kv_dim0 + kvh * hd;
+    // Q80: the scale planes, f16 [rows, kv_dim0/32], from the same cache row
+    [[maybe_unused]] const int nblk = kv_dim0 / QB;
+    [[maybe_unused]] const _Float16 *ks = nullptr, *vs = nullptr;
+    if constexpr (Q8) {
+        const int64_t sb = rows.cache_base(b0) * nblk + kvh * (hd / QB);
+        ks = reinterpret_cast<const _Float16 *>(rows.ks) + sb;
+        vs = reinterpret_cast<const _Float16 *>(rows.vs) + sb;
+    }
 
-    // staging: thread holds NLD 16-byte chunks of the K tile and of the V
-    // tile in registers between their global load and their LDS store. A
-    // timestep at or past maxlen (last tile only) re-reads row maxlen-1: a
-    // valid row, masked below.
-    v8h_t kreg[NLD], vreg[NLD];
+    // staging: thread holds NLD 8-element chunks of the K tile and of the V
+    // tile in registers between their global load and their LDS store: 16
+    // bytes of f16, or 8 bytes of Q80 codes and their block's f16 scale,
+    // which tile_store turns into the same f16 tile (code * d rounded to f16
+    // once). A timestep at or past maxlen (last tile only) re-reads row
+    // maxlen-1: a valid row, masked below.
+    //
+    // Paged: the cache row of a timestep comes from the run's page list (all
+    // rows of a run are one sequence: b0's). The clamp keeps every lookup
+    // below maxlen, in pages the host checked to be mapped, and inside the
+    // tile, so with pages of 32 rows or more the whole tile lies in one
+    // page: one workgroup-uniform id per tile. Smaller pages look up per
+    // thread (the threads of a timestep share the address). page_fetch runs
+    // one tile ahead of tile_load, itself one tile ahead of use: neither the
+    // K/V loads nor the MFMA phase ever wait on a table lookup in flight.
+    using Staged = std::conditional_t<Q8, int2, v8h_t>;
+    Staged kreg[NLD], vreg[NLD];
+    [[maybe_unused]] _Float16 kscl[NLD], vscl[NLD];
+    [[maybe_unused]] int pgid[NLD];  // page of each chunk of the next tile_load
+    [[maybe_unused]] const int *seqp = nullptr;
+    if constexpr (ROWS::kPaged)
+        seqp = rows.pages + __builtin_amdgcn_readfirstlane(rows.rows[2 * b0]);
+    auto page_fetch = [&](int tile) {
+        if constexpr (ROWS::kPaged) {
+            if (tile * CHUNK_T >= maxlen) return;  // no such tile
+            if (rows.shift >= 5) {
+                const int id = seqp[(tile * CHUNK_T) >> rows.shift];
+                #pragma unroll
+                for (int it = 0; it < NLD; it++) pgid[it] = id;
+            } else {
+                #pragma unroll
+                for (int it = 0; it < NLD; it++) {
+                    const int idx = threadIdx.x + it * CHUNK_NW * WAVE;
+                    const int t = min(tile * CHUNK_T + idx / DCH, maxlen - 1);
+                    pgid[it] = seqp[t >> rows.shift];
+                }
+            }
+        }
+    };
     auto tile_load = [&](int tile) {
         #pragma unroll
         for (int it = 0; it < NLD; it++) {
             const int idx = threadIdx.x + it * CHUNK_NW * WAVE;
             const int t = min(tile * CHUNK_T + idx / DCH, maxlen - 1);
-            const int64_t off = (int64_t)t * kv_dim0 + (idx % DCH) * 8;
-            kreg[it] = *reinterpret_cast<const v8h_t *>(kc + off);
-            vreg[it] = *reinterpret_cast<const v8h_t *>(vc + off);
+            int64_t r = t;
+            if constexpr (ROWS::kPaged)
+                r = ((int64_t)pgid[it] << rows.shift)
+                  + (t & ((1 << rows.shift) - 1));
+            const int64_t off = r * kv_dim0 + (idx % DCH) * 8;
+            kreg[it] = *reinterpret_cast<const Staged *>(kc + off);
+            vreg[it] = *reinterpret_cast<const Staged *>(vc + off);
+            if constexpr (Q8) {
+                const int64_t so = r * nblk + (idx % DCH) * 8 / QB;
+                kscl[it] = ks[so];
+                vscl[it] = vs[so];
+            }
         }
     };
     auto tile_store = [&](int buf) {
@@ -847,9 +919,17 @@ k_attn_chunk(const float *__restrict__ q, int q_ld,
         for (int it = 0; it < NLD; it++) {
             const int idx = threadIdx.x + it * CHUNK_NW * WAVE;
             const int t = idx / DCH, d = (idx % DCH) * 8;
-            *reinterpret_cast<v8h_t *>(&sk[buf][t * KLD + d]) = kreg[it];
+            v8h_t kh, vh;
+            if constexpr (Q8) {
+                kh = q80_codes_f16(kreg[it], kscl[it]);
+                vh = q80_codes_f16(vreg[it], vscl[it]);
+            } else {
+                kh = kreg[it];
+                vh = vreg[it];
+            }
+            *reinterpret_cast<v8h_t *>(&sk[buf][t * KLD + d]) = kh;
             #pragma unroll
-            for (int i = 0; i < 8; i++) sv[buf][(d + i) * VLD + t] = vreg[it][i];
+            for (int i = 0; i < 8; i++) sv[buf][(d + i) * VLD + t] = vh[i];
         }
     };
 
@@ -887,14 +967,19 @@ k_attn_chunk(const float *__restrict__ q, int q_ld,
         // is multiplied; one barrier per tile (the buffer stored to at the
         // end of an iteration was last read before the previous barrier)
         int tile = sp, buf = 0;
+        page_fetch(tile);
         if (tile * CHUNK_T < maxlen) {
             tile_load(tile);
+            page_fetch(tile + S);
             tile_store(0);
         }
         __syncthreads();
         for (; tile * CHUNK_T < maxlen; tile += S, buf ^= 1) {
             const bool more = (tile + S) * CHUNK_T < maxlen;
-            if (more) tile_load(tile + S);
+            if (more) {
+                tile_load(tile + S);
+                page_fetch(tile + 2 * S);
+            }
             if (active) {
                 const int t0 = tile * CHUNK_T;
                 v16f_t s;
@@ -1592,12 +1677,17 @@ static void attn_chunk_launch(const char *name, const char *other,
                               const OptTensor &k_scales,
                               const OptTensor &v_scales) {
     CHECK_CUDA(q);
-    TORCH_CHECK(kc.scalar_type() == at::kHalf && vc.scalar_type() == at::kHalf,
-                name, " serves a float16 KV cache only: use ", other,
-                " for a float32 or int8 (Q80) cache");
-    TORCH_CHECK(!k_scales.has_value() && !v_scales.has_value(), name,
-                " takes no k_scales / v_scales: use ", other,
-                " for a Q80 KV cache");
+    const bool f16 = kc.scalar_type() == at::kHalf
+                  && vc.scalar_type() == at::kHalf;
+    const bool q80 = kc.scalar_type() == at::kChar
+                  && vc.scalar_type() == at::kChar;
+    TORCH_CHECK(f16 || q80, name, " serves a float16 or an int8 (Q80) KV "
+                "cache: use ", other, " for a float32 cache");
+    TORCH_CHECK(q80 || (!k_scales.has_value() && !v_scales.has_value()), name,
+                " takes k_scales / v_scales with an int8 (Q80) KV cache only");
+    TORCH_CHECK(f16 || (k_scales.has_value() && v_scales.has_value()), name,
+                ": an int8 (Q80) KV cache needs k_scales= and v_scales=");
+    const KVScales sc = kv_scales(kc, vc, k_scales, v_scales);
     TORCH_CHECK(head_dim == 64 || head_dim == 128, name,
                 " serves head_dim 64 and 128 (got ", head_dim, "): use ", other);
     TORCH_CHECK(batch >= 1 && n_runs >= 1 && batch <= n_runs * CHUNK_ROWS, name,
@@ -1621,17 +1711,24 @@ static void attn_chunk_launch(const char *name, const char *other,
     const dim3 grid(n_heads0 / kv_mul, n_runs, splits);
     with_head_vec(head_dim, [&](auto vec_const) {
         constexpr int V = decltype(vec_const)::value;
-        hipLaunchKernelGGL((k_attn_chunk<V, ROWS>), grid,
-                           dim3(CHUNK_NW * WAVE), 0, cur_stream(),
-                           q.data_ptr<float>(), (int)q_ld,
-                           reinterpret_cast<const __half *>(
-                               kc.data_ptr<at::Half>()),
-                           reinterpret_cast<const __half *>(
-                               vc.data_ptr<at::Half>()),
-                           rows, runs, (int)batch, (int)n_heads0, (int)kv_mul,
-                           (int)kc.size(1), 1.0f / sqrtf((float)head_dim),
-                           ml_scratch.data_ptr<float>(),
-                           o_scratch.data_ptr<float>());
+        with_kv_ptrs(kc, vc, [&](auto *kcp, auto *vcp) {
+            using KVT = std::remove_pointer_t<decltype(kcp)>;
+            auto launch = [&](auto krows) {
+                hipLaunchKernelGGL((k_attn_chunk<V, KVT, decltype(krows)>),
+                                   grid, dim3(CHUNK_NW * WAVE), 0,
+                                   cur_stream(), q.data_ptr<float>(),
+                                   (int)q_ld, kcp, vcp, krows, runs,
+                                   (int)batch, (int)n_heads0, (int)kv_mul,
+                                   (int)kc.size(1),
+                                   1.0f / sqrtf((float)head_dim),
+                                   ml_scratch.data_ptr<float>(),
+                                   o_scratch.data_ptr<float>());
+            };
+            if constexpr (kKVQ80<KVT>)
+                launch(Q80Rows<ROWS>{rows, sc.k, sc.v});
+            else if constexpr (std::is_same_v<KVT, __half>)
+                launch(rows);
+        });
         combine_launch<V>(ml_scratch, o_scratch, yp, zqp, zsp, zbsp, batch,
                           n_heads0, splits);
     });
@@ -1652,8 +1749,20 @@ void attn_chunk(torch::Tensor q, int64_t q_ld, torch::Tensor kc,
                       zbs, k_scales, v_scales);
 }
 
-// attn_rows with the rows grouped into runs: int32 [n_runs, 2] = {first
-// batch row, row count}, each run consecutive rows of one sequence.
+// A run table as the kernel reads it: int32 [>= n_runs, 2] = {first batch
+// row, row count}, each run consecutive rows of one sequence.
+static const int *run_table(const torch::Tensor &runs, int64_t n_runs,
+                            const torch::Tensor &kc, const char *other) {
+    TORCH_CHECK(runs.is_cuda() && runs.scalar_type() == at::kInt
+                && runs.dim() == 2 && runs.size(1) == 2 && runs.is_contiguous()
+                && n_runs >= 1 && runs.size(0) >= n_runs
+                && runs.device() == kc.device(),
+                "run table must be a contiguous int32 [>= n_runs, 2] on the "
+                "cache's device (or use ", other, ")");
+    return runs.data_ptr<int>();
+}
+
+// attn_rows with the rows grouped into runs.
 void attn_chunk_rows(torch::Tensor q, int64_t q_ld, torch::Tensor kc,
                      torch::Tensor vc, torch::Tensor y, torch::Tensor rows,
                      torch::Tensor runs, int64_t n_runs, int64_t batch,
@@ -1663,16 +1772,31 @@ void attn_chunk_rows(torch::Tensor q, int64_t q_ld, torch::Tensor kc,
                      OptTensor zs = c10::nullopt, OptTensor zbs = c10::nullopt,
                      OptTensor k_scales = c10::nullopt,
                      OptTensor v_scales = c10::nullopt) {
-    TORCH_CHECK(runs.is_cuda() && runs.scalar_type() == at::kInt
-                && runs.dim() == 2 && runs.size(1) == 2 && runs.is_contiguous()
-                && n_runs >= 1 && runs.size(0) >= n_runs
-                && runs.device() == kc.device(),
-                "run table must be a contiguous int32 [>= n_runs, 2] on the "
-                "cache's device (or use attn_rows)");
+    const int *runp = run_table(runs, n_runs, kc, "attn_rows");
     attn_chunk_launch("attn_chunk_rows", "attn_rows", q, q_ld, kc, vc, y,
-                      table_rows(rows, batch), runs.data_ptr<int>(), n_runs,
+                      table_rows(rows, batch), runp, n_runs,
                       batch, n_heads0, kv_mul, head_dim, splits, ml_scratch,
                       o_scratch, zq, zs, zbs, k_scales, v_scales);
+}
+
+// attn_paged with the rows grouped into runs: every timestep of a run is
+// found through the page list of the run's sequence.
+void attn_chunk_paged(torch::Tensor q, int64_t q_ld, torch::Tensor kc,
+                      torch::Tensor vc, torch::Tensor y, torch::Tensor rows,
+                      torch::Tensor page_table, int64_t page_size,
+                      torch::Tensor runs, int64_t n_runs, int64_t batch,
+                      int64_t n_heads0, int64_t kv_mul, int64_t head_dim,
+                      int64_t splits, torch::Tensor ml_scratch,
+                      torch::Tensor o_scratch, OptTensor zq = c10::nullopt,
+                      OptTensor zs = c10::nullopt, OptTensor zbs = c10::nullopt,
+                      OptTensor k_scales = c10::nullopt,
+                      OptTensor v_scales = c10::nullopt) {
+    const int *runp = run_table(runs, n_runs, kc, "attn_paged");
+    TORCH_CHECK(kc.dim() == 2, "attn_chunk_paged: caches are [rows, kv_dim0]");
+    attn_chunk_launch("attn_chunk_paged", "attn_paged", q, q_ld, kc, vc, y,
+                      paged_rows(rows, page_table, page_size, batch, kc), runp,
+                      n_runs, batch, n_heads0, kv_mul, head_dim, splits,
+                      ml_scratch, o_scratch, zq, zs, zbs, k_scales, v_scales);
 }
 
 // The Q80 write kernel for either launcher below; mode as k_rope_kv_q80's
@@ -1892,6 +2016,14 @@ void register_attn(py::module &m) {
           py::arg("runs"), py::arg("n_runs"), py::arg("batch"),
           py::arg("n_heads0"), py::arg("kv_mul"), py::arg("head_dim"),
           py::arg("splits"), py::arg("ml_scratch"), py::arg("o_scratch"),
+          py::arg("zq") = py::none(), py::arg("zs") = py::none(),
+          py::arg("zbs") = py::none(), KV_SCALE_ARGS);
+    m.def("attn_chunk_paged", &attn_chunk_paged, py::arg("q"), py::arg("q_ld"),
+          py::arg("kc"), py::arg("vc"), py::arg("y"), py::arg("rows"),
+          py::arg("page_table"), py::arg("page_size"), py::arg("runs"),
+          py::arg("n_runs"), py::arg("batch"), py::arg("n_heads0"),
+          py::arg("kv_mul"), py::arg("head_dim"), py::arg("splits"),
+          py::arg("ml_scratch"), py::arg("o_scratch"),
           py::arg("zq") = py::none(), py::arg("zs") = py::none(),
           py::arg("zbs") = py::none(), KV_SCALE_ARGS);
     m.def("kv_append", &kv_append);

@@ -105,6 +105,99 @@ def chunk_ab(positions=(512, 2048, 4096, 8192), batches=(32,), rounds=3,
                   + f"  max |dcode| {diff}")
 
 
+def chunk_forms_ab(kv_dtype="f16", page_size=0, positions=(512, 2048, 4096, 8192),
+                   batches=(32,), rounds=3):
+    """The paged and Q80 forms of the chunk attention in an isolated hipGraph
+    at the 8B shape (Q80 output), B rows of one sequence at first position p,
+    at the S a row step of the decode schedule takes there (16 below 2048,
+    else 32). Columns, interleaved over `rounds`, median us per call:
+
+      parent      what such a step launches with the option off: attn_paged
+                  with --page-size, else attn_rows (k_attn_split + combine)
+      chunk       attn_chunk_paged / attn_chunk_rows on the same cache
+      chunk flat  (--page-size) attn_chunk_rows on the same rows unpaged:
+                  the difference to `chunk` is the cost of the page lookup
+      chunk f16   (--kv-dtype q80) the same form on the dequantised values
+                  as an f16 cache: what the halved loads bring
+
+    Pages are mapped in a scrambled order.
+
+      python tools/kernel_bench.py chunk --page-size 64
+      python tools/kernel_bench.py chunk --kv-dtype q80 [--page-size 64]
+      python tools/kernel_bench.py chunk-rows --kv-dtype q80     B = 4 .. 32"""
+    H0, hd, kvd, kv_mul = 32, 128, 1024, 4
+    P, q80 = page_size, kv_dtype == "q80"
+    seq = (max(positions) + 64 + 255) // 256 * 256
+    if q80:
+        flat = [torch.randint(-127, 128, (seq, kvd), device=dev, generator=g)
+                .to(torch.int8) for _ in range(2)]
+        flat += [(a / 127 * (0.5 + torch.rand(seq, kvd // 32, device=dev,
+                                              generator=g))).half()
+                 for a in (0.3, 1.0)]
+        f16 = [(c.float() * s.float().repeat_interleave(32, dim=1)).half()
+               for c, s in zip(flat[:2], flat[2:])]
+    else:
+        flat = [(torch.randn(seq, kvd, device=dev, generator=g) * 0.3).half(),
+                torch.randn(seq, kvd, device=dev, generator=g).half()]
+
+    def i32(x):
+        return torch.tensor(x, dtype=torch.int32, device=dev)
+
+    def scales(planes):
+        return dict(zip(("k_scales", "v_scales"), planes[2:]))
+
+    if P:  # pool row perm[j] * P + i holds flat row j * P + i
+        perm = torch.randperm(seq // P, device=dev, generator=g)
+        src = (perm.argsort()[:, None] * P
+               + torch.arange(P, device=dev)).reshape(-1)
+        pool = [t[src] for t in flat]
+        pt = perm.to(torch.int32).reshape(1, -1).contiguous()
+    print(f"\n-- chunk attention forms, isolated graph, 8B shape, {kv_dtype} KV"
+          f"{f', pages of {P}' if P else ''}, Q80 out (median us per call) --")
+    for B in batches:
+        qv = torch.randn(B, H0 * hd, device=dev, generator=g)
+        y = torch.zeros(B, H0 * hd, device=dev)
+        z = [torch.zeros(B, H0 * hd, dtype=torch.int8, device=dev),
+             torch.zeros(B, H0 * hd // 32, device=dev),
+             torch.zeros(B, H0 * hd // 32, device=dev)]
+        runs = i32([[0, B]])
+        for p in positions:
+            S = 16 if p < 2048 else 32
+            rows = i32([[0, p + b] for b in range(B)])
+            ml = torch.zeros(B * H0 * S * 2, device=dev)
+            osc = torch.zeros(B * H0 * S * hd, device=dev)
+            tail = (B, H0, kv_mul, hd, S, ml, osc, *z)
+
+            def rows_form(planes, chunk):
+                if chunk:
+                    return lambda: k.attn_chunk_rows(
+                        qv, H0 * hd, *planes[:2], y, rows, runs, 1, *tail,
+                        **scales(planes))
+                return lambda: k.attn_rows(qv, H0 * hd, *planes[:2], y, rows,
+                                           *tail, **scales(planes))
+
+            def paged_form(chunk):
+                if chunk:
+                    return lambda: k.attn_chunk_paged(
+                        qv, H0 * hd, *pool[:2], y, rows, pt, P, runs, 1, *tail,
+                        **scales(pool))
+                return lambda: k.attn_paged(qv, H0 * hd, *pool[:2], y, rows, pt,
+                                            P, *tail, **scales(pool))
+
+            form = paged_form if P else lambda c: rows_form(flat, c)
+            cands = {"parent": form(False), "chunk": form(True)}
+            if P:
+                cands["chunk flat"] = rows_form(flat, True)
+            if q80:
+                cands["chunk f16"] = rows_form(f16, True)
+            t = {name: [] for name in cands}
+            for _ in range(rounds):
+                for name, fn in cands.items():
+                    t[name].append(bench(fn, n=16, reps=3))
+            print(f"B={B:2d} pos={p:5d} S={S:2d}  " + "  ".join(
+                f"{name}: {statistics.median(v):7.1f}" for name, v in t.items()))
+
+
 def resid_ab(rounds=5, forms=(16, 8, 4)):
     """q40_gemv_resid_q alone in an isolated hipGraph at the down-projection
     shapes (wo, w2) of the 1B, 3B, 8B and 70B presets, one column per
@@ -173,6 +266,17 @@ def resid_ab(rounds=5, forms=(16, 8, 4)):
 
 if sys.argv[1:] == ["attn"]:
     attn_ab()
+    sys.exit(0)
+if sys.argv[1:2] in (["chunk"], ["chunk-rows"]) and len(sys.argv) > 2:
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("mode")
+    ap.add_argument("--kv-dtype", choices=("f16", "q80"), default="f16")
+    ap.add_argument("--page-size", type=int, default=0)
+    a = ap.parse_args()
+    rows = (dict(positions=(512, 4096), batches=(4, 8, 16, 32))
+            if a.mode == "chunk-rows" else {})
+    chunk_forms_ab(a.kv_dtype, a.page_size, **rows)
     sys.exit(0)
 if sys.argv[1:] == ["chunk"]:
     chunk_ab()

@@ -5,29 +5,51 @@ setting: ms and tok/s of every repetition (each pays its own prefill-graph
 captures, which the switch drops: the same cost in both settings), and the
 tok/s of the last 512 tokens alone, where the context is longest.
 
-  python tools/prefill_probe.py [lengths...]      default 512 2048 8192"""
-import os, sys, time, torch
+  python tools/prefill_probe.py [lengths...]      default 512 2048 8192
+    --kv-dtype q80             a Q80 KV cache; "on" is set_chunk_attn(True, q80=True)
+    --kv-pages M --page-size P a paged cache: the prompt goes through
+                               forward_rows into slot 0, whose pages are mapped
+                               in a scrambled order (M * P >= the longest prompt)"""
+import argparse, os, sys, time, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from dllama_amd.model_file import preset_header
 from dllama_amd.models.config import ModelConfig
 from dllama_amd.models.hip_model import HipTransformer
 
-lengths = [int(a) for a in sys.argv[1:]] or [512, 2048, 8192]
+ap = argparse.ArgumentParser()
+ap.add_argument("lengths", type=int, nargs="*", default=[512, 2048, 8192])
+ap.add_argument("--kv-dtype", choices=("f16", "q80"), default="f16")
+ap.add_argument("--kv-pages", type=int, default=0)
+ap.add_argument("--page-size", type=int, default=64)
+a = ap.parse_args()
+lengths, q80 = a.lengths, a.kv_dtype == "q80"
 h = preset_header("llama-3.1-8b", seq_len=max(lengths))
 cfg = ModelConfig.from_header(h)
-m = HipTransformer.synthetic(cfg)
+m = HipTransformer.synthetic(cfg, kv_dtype=a.kv_dtype, kv_pages=a.kv_pages,
+                             page_size=a.page_size)
 prompt = torch.randint(0, 128256, (max(lengths),))
+if a.kv_pages:
+    need = -(-max(lengths) // a.page_size)
+    m.set_slot_pages(0, torch.randperm(a.kv_pages)[:need].tolist())
+
+
+def step(i):
+    if a.kv_pages:
+        m.forward_rows(prompt[i:i+32].tolist(), [0] * 32, list(range(i, i+32)))
+    else:
+        m.forward(prompt[i:i+32], torch.arange(i, i+32))
 
 
 def prefill(n):
     """(seconds for n tokens, seconds for the last 512 of them)."""
-    m.pos.fill_(0)
+    if not a.kv_pages:
+        m.pos.fill_(0)
     torch.cuda.synchronize(); t0 = t_tail = time.perf_counter()
     for i in range(0, n, 32):
         if i == n - 512:
             torch.cuda.synchronize(); t_tail = time.perf_counter()
         m.skip_logits = i < n - 32
-        m.forward(prompt[i:i+32], torch.arange(i, i+32))
+        step(i)
         m.skip_logits = False
     torch.cuda.synchronize()
     t1 = time.perf_counter()
@@ -37,7 +59,7 @@ def prefill(n):
 for n in lengths:
     for rep in range(3):
         for on in (False, True):
-            m.set_chunk_attn(on)
+            m.set_chunk_attn(on, q80=q80)
             dt, tail = prefill(n)
             print(f"prefill {n:5d} tokens, chunk attn {'on ' if on else 'off'}: "
                   f"{dt*1000:8.1f} ms = {n/dt:6.0f} tok/s; last 512: "
