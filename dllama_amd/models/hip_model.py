@@ -55,6 +55,11 @@ from .config import ModelConfig
 from .graphs import StepGraphs, capture_hip_graph
 
 QB = 32
+# the MoE routing plan (csrc/dllama_common.h, "MoE plan"): tile count, the
+# slot permutation, then {expert, first, count} per tile
+MOE_PLAN_MAX_SLOTS = 512
+MOE_PLAN_INTS = 4 + MOE_PLAN_MAX_SLOTS + 3 * (MOE_PLAN_MAX_SLOTS
+                                              + MOE_PLAN_MAX_SLOTS // 32)
 # logprob_rows results per row: f32 {lse, logprob, top-20 logprobs} and i32
 # top-20 ids; with the row's {token, status} that is LP_WORDS int64 words
 LP_MAXK = R.LOGPROB_MAXK
@@ -285,6 +290,14 @@ class HipTransformer:
         # pair, and per-wave gate recompute adds ~8 us to each MoE consumer
         self.fused_ffn = flag("DLLAMA_FUSED_FFN", "0")
         self.fused_moe = flag("DLLAMA_FUSED_MOE", "0")
+        # multi-row MoE steps on the matrix cores: from moe_gemm_min_rows
+        # (padded) rows the step's slots are sorted by expert (moe_group) and
+        # the expert matmuls run as q40_gemm_grouped, an expert's weights
+        # read once per step (docs/DESIGN.md §11). Measured slower than the
+        # grouped GEMV at every row count (profiles/r15_moe_gemm.md), so
+        # off, and min_rows has no crossover to come from: it keeps 8
+        self.moe_gemm = flag("DLLAMA_MOE_GEMM", "0")
+        self.moe_gemm_min_rows = 8
         # deferred-quant dense decode (EPI_RESID_Q + PRO2); =0 reverts to
         # explicit norm_quant launches
         self.use_deferred = flag("DLLAMA_DEFERRED", "1")
@@ -464,6 +477,9 @@ class HipTransformer:
             self.moe_out13 = torch.zeros(S, 2 * c.ff_dim0, device=dev)
             self.moe_dq = QuantBuf(S, c.ff_dim0, dev)
             self.moe_y = torch.zeros(S, c.dim, device=dev)
+            # the routing plan of a step that takes the grouped GEMM
+            self.moe_plan = torch.zeros(MOE_PLAN_INTS, dtype=torch.int32,
+                                        device=dev)
 
     def _alloc_attn_scratch(self):
         """Flash-decode split scratch sized for the current S (the adaptive
@@ -646,6 +662,13 @@ class HipTransformer:
         one kernel or the other."""
         self.chunk_attn = bool(on)
         self.chunk_attn_q80 = bool(on) and bool(q80)
+        self.graphs.clear()
+
+    def set_moe_gemm(self, on: bool = True):
+        """Multi-row MoE steps take the expert-grouped MFMA GEMM (or stop
+        taking it). Drops the captured graphs: a step's graph holds one set
+        of launches or the other."""
+        self.moe_gemm = bool(on)
         self.graphs.clear()
 
     def _swiglu_q80(self, out13, rows: int, qb: QuantBuf, *act):
@@ -979,6 +1002,26 @@ class HipTransformer:
             k.q40_gemv_grouped(lw["w2"].qs, lw["w2"].scales,
                                *self.moe_dq.triple(), self.moe_idx[:S],
                                self.moe_y, 1, router=wts, topk=ka, n_slots=S)
+        elif (self.moe_gemm and NB >= self.moe_gemm_min_rows
+              and S <= MOE_PLAN_MAX_SLOTS):
+            # expert-major: slots sorted by expert, each expert's weights
+            # read once for all the rows that chose it
+            wts, gate = self.moe_wts, {}
+            k.moe_gate(self.moe_router[:NB], self.moe_idx, self.moe_wts, NB, ka)
+            k.moe_group(self.moe_idx[:S], self.moe_plan, c.n_experts)
+            xq = self.xq.triple()[:2]
+            if c.ff_dim0 % 32 == 0:
+                dq = self.moe_dq
+                k.q40_gemm_grouped(lw["w13"].qs, lw["w13"].scales, *xq,
+                                   self.moe_plan, S, ka,
+                                   oq=dq.q, os=dq.s, obs=dq.bs)
+            else:
+                k.q40_gemm_grouped(lw["w13"].qs, lw["w13"].scales, *xq,
+                                   self.moe_plan, S, ka, y=self.moe_out13)
+                self._swiglu_q80(self.moe_out13, S, self.moe_dq)
+            k.q40_gemm_grouped(lw["w2"].qs, lw["w2"].scales,
+                               *self.moe_dq.triple()[:2], self.moe_plan, S, 1,
+                               y=self.moe_y)
         else:
             wts, gate = self.moe_wts, {}
             k.moe_gate(self.moe_router[:NB], self.moe_idx, self.moe_wts, NB, ka)

@@ -765,19 +765,9 @@ typedef _Float16 v4h_t __attribute__((ext_vector_type(4)));
 typedef float v16f_t __attribute__((ext_vector_type(16)));
 
 // The kernel's independent f32 multiplies and fmas (the accumulator rescale,
-// the q scaling, the softmax exponents), spelled as the scalar-per-lane
-// instruction: the compiler would pair them into packed f32 VALU ops, which
-// this kernel keeps out (checked in its disassembly: no v_pk_*_f32).
-__device__ __forceinline__ float mul_f32(float a, float b) {
-    float r;
-    asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float fma_f32(float a, float b, float c) {
-    float r;
-    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
+// the q scaling, the softmax exponents) go through mul_f32 / fma_f32
+// (dllama_common.h), which keep packed f32 VALU ops out of this kernel
+// (checked in its disassembly: no v_pk_*_f32).
 
 constexpr int CHUNK_T = 32;     // timesteps per tile = MFMA M of the scores
 constexpr int CHUNK_ROWS = 32;  // query rows per run = MFMA N

@@ -48,6 +48,21 @@ __device__ __forceinline__ int dot4(int a, int b, int c) {
 }
 #endif
 
+// One f32 multiply or fma spelled as the scalar-per-lane instruction: the
+// compiler would pair independent ones into packed f32 VALU ops, which the
+// kernels that call these keep out (checked in their disassembly: no
+// v_pk_*_f32).
+__device__ __forceinline__ float mul_f32(float a, float b) {
+    float r;
+    asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ float fma_f32(float a, float b, float c) {
+    float r;
+    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+
 __device__ __forceinline__ float wave_reduce_sum(float v) {
     #pragma unroll
     for (int off = 32; off > 0; off >>= 1)
@@ -149,6 +164,30 @@ __device__ __forceinline__ void moe_gate_wave(
     for (int t = 0; t < 16; t++)
         out_w[t] = t < topk ? chosen[t] * winv : 0.0f;
 }
+
+// ---------------------------------------------------------------- MoE plan
+// The routing plan of one multi-row MoE step, written by k_moe_group
+// (moe.hip) and read by k_q40_gemm_grouped (gemm.hip). One int32 buffer:
+//   [0]                     number of live tiles
+//   [MOE_PLAN_PERM + i]     perm: the step's slots ordered by (expert, slot)
+//   [MOE_PLAN_TILES + 3*t]  tile t = {expert, first, count}: columns
+//                           perm[first .. first+count), count <= 32
+// The offsets are fixed, so one buffer serves every S <= MOE_PLAN_MAX_SLOTS.
+#define MOE_TILE 32
+#define MOE_PLAN_MAX_SLOTS 512
+#define MOE_PLAN_PERM 4
+#define MOE_PLAN_TILES (MOE_PLAN_PERM + MOE_PLAN_MAX_SLOTS)
+
+// Upper bound of the live tile count for any routing of S slots over E
+// experts: every expert that has a slot opens one tile, and each further
+// tile of an expert holds 32 slots of its own. Fixed per (E, S), so it can
+// be a captured launch's grid.
+static inline int moe_max_tiles(int n_experts, int n_slots) {
+    return (n_experts < n_slots ? n_experts : n_slots) + n_slots / MOE_TILE;
+}
+
+#define MOE_PLAN_INTS \
+    (MOE_PLAN_TILES + 3 * (MOE_PLAN_MAX_SLOTS + MOE_PLAN_MAX_SLOTS / MOE_TILE))
 
 // ---------------------------------------------------------------- Q80 block
 // One Q80 block held one value per lane by a 32-lane group: the block scale

@@ -253,6 +253,238 @@ __global__ void k_gemm_reduce(const float *__restrict__ part,
     }
 }
 
+// ------------------------------------------- expert-grouped GEMM (MoE steps)
+// The MoE matmul of a multi-row step, expert by expert: k_moe_group (moe.hip)
+// has sorted the step's (row, k) slots by expert into tiles of at most 32
+// slots of one expert, and a workgroup here computes one tile against 128
+// weight rows of that expert, so an expert's weights are read once per step
+// however many rows chose it (k_q40_gemv_grouped streams the expert once per
+// slot, on the VALU).
+//
+// Work split: grid (ceil(d / 128), moe_max_tiles). grid.y is the routing-
+// independent bound, so a captured step replays for any routing; a workgroup
+// at or past the live tile count leaves on a uniform branch. Wave w owns 32
+// weight rows of the expert in the stacked [E, rows, n/2] planes, the tile's
+// slots are the MFMA N dimension: one v_mfma_i32_32x32x32_i8 per Q40 block
+// and chain, descaled by sw * sx into f32 exactly as k_q40_gemm_v2 does
+// (K = 32 is the quantisation block, so the per-block scales stay exact).
+//
+// Activations are gathered: column c of the tile is slot perm[first + c] and
+// reads input row slot / k_slots (k_slots = topk where the slots of a row
+// share it, 1 where every slot has a row of its own). Thread t stages block
+// t / 32 of column t % 32 of an 8-block chunk: loaded into registers before
+// the chunk's MFMAs and written to the other LDS buffer after them, shared
+// by the 4 waves. A column at or past `count` is staged as zero codes with a
+// zero scale and no address is formed for it. Columns never mix: a slot's
+// result does not depend on what shares its tile.
+//
+// Weights come through a 4-block register ring, three loads ahead of the
+// MFMA (the comment at the ring says why it is not v2's cur/next pair).
+//
+// Epilogues. GEPI_PLAIN stores f32 y[slot][row] for c < count. GEPI_SILU /
+// GEPI_GELU (d = ff, ff % 32 == 0): the wave also owns rows ff + m .. of the
+// same expert (W3 under W1), two independent MFMA chains per block on one A
+// fragment, forms act(a) * g in registers as k_swiglu_q80 computes it, and
+// emits the Q80 triple [S, ff]: in the C layout the 32 lanes of a half-wave
+// hold one slot's 32 consecutive ff indices, one Q80 block.
+//
+// No K-split: at Qwen3-30B-A3B shapes a 32-row chunk already launches about
+// 12 x 112 (W1|W3) and 16 x 112 (W2) live workgroups on 256 CUs.
+enum { GEPI_PLAIN = 0, GEPI_SILU = 1, GEPI_GELU = 2 };
+#define GEMM_GROUPED_RING 4
+static_assert(GEMM_V2_CHUNK % GEMM_GROUPED_RING == 0, "ring indices are per-chunk constants");
+
+template <int EPI>
+__global__ void __launch_bounds__(256)
+k_q40_gemm_grouped(const uint8_t *__restrict__ qs,
+                   const __half *__restrict__ scales,
+                   const int8_t *__restrict__ xq,
+                   const float *__restrict__ xs,
+                   const int *__restrict__ plan,
+                   float *__restrict__ y,
+                   int8_t *__restrict__ oq,
+                   float *__restrict__ os,
+                   float *__restrict__ obs,
+                   int d, int n, int n_experts, int n_slots, int k_slots) {
+    constexpr bool SWIGLU = EPI != GEPI_PLAIN;
+    __shared__ int8_t lds_a[2][GEMM_V2_CHUNK][MOE_TILE][QB];
+    __shared__ float lds_s[2][GEMM_V2_CHUNK][MOE_TILE];
+    __shared__ int lds_slot[MOE_TILE];  // slot of column c, -1 past count
+    const int tile = blockIdx.y;
+    if (tile >= plan[0]) return;  // workgroup-uniform
+    const int *tp = plan + MOE_PLAN_TILES + 3 * tile;
+    // a plan is trusted for its order, not for memory safety: the expert
+    // and the columns are clamped to what the buffers hold
+    const int e = min(max(tp[0], 0), n_experts - 1);
+    const int first = max(tp[1], 0);
+    const int count = min(min(tp[2], MOE_TILE), n_slots - first);
+
+    const int tid = threadIdx.x;
+    const int wave = tid / WAVE;
+    const int lane = tid % WAVE;
+    const int khi = lane >> 5;
+    const int mcol = lane & 31;
+    const int mbase = (blockIdx.x * 4 + wave) * 32;
+    const bool live = mbase < d;  // wave-uniform
+    const int mrow = min(mbase + mcol, d - 1);
+    const int nb = n / QB;
+    // the expert's planes hold W1 over W3 in the SwiGLU form
+    const int64_t row_a = (int64_t)e * (SWIGLU ? 2 * d : d) + mrow;
+    const uint4 *wrow_a = reinterpret_cast<const uint4 *>(qs + row_a * (n >> 1));
+    const __half *srow_a = scales + row_a * nb;
+    const uint4 *wrow_g = wrow_a + (int64_t)d * (n >> 5);  // d rows of n/32 uint4
+    const __half *srow_g = srow_a + (int64_t)d * nb;
+
+    // this thread's share of every staged chunk: block sblk of column scol
+    const int scol = tid & 31;
+    const int sblk = tid >> 5;
+    const int my_slot = scol < count ? plan[MOE_PLAN_PERM + first + scol] : -1;
+    if (tid < MOE_TILE) lds_slot[tid] = my_slot;
+    uint4 sa0, sa1;
+    float ssx;
+    auto stage_load = [&](int jc) {
+        sa0 = make_uint4(0, 0, 0, 0);
+        sa1 = sa0;
+        ssx = 0.0f;
+        if (my_slot >= 0 && jc + sblk < nb) {
+            const int64_t xr = my_slot / k_slots;
+            const uint4 *p = reinterpret_cast<const uint4 *>(
+                xq + xr * n + (jc + sblk) * QB);
+            sa0 = p[0];
+            sa1 = p[1];
+            ssx = xs[xr * nb + jc + sblk];
+        }
+    };
+    auto stage_store = [&](int buf) {
+        *reinterpret_cast<uint4 *>(&lds_a[buf][sblk][scol][0]) = sa0;
+        *reinterpret_cast<uint4 *>(&lds_a[buf][sblk][scol][16]) = sa1;
+        lds_s[buf][sblk][scol] = ssx;
+    };
+    auto extract = [&](const uint4 &wq, v4i32_t &b) {
+        const uint32_t wv[4] = {wq.x, wq.y, wq.z, wq.w};
+        #pragma unroll
+        for (int t = 0; t < 4; t++) {
+            uint32_t s = khi ? ((wv[t] >> 4) & 0x0F0F0F0Fu) : (wv[t] & 0x0F0F0F0Fu);
+            s ^= 0x08080808u;
+            b[t] = (int)(s | (((s >> 3) & 0x01010101u) * 0xF0u));
+        }
+    };
+
+    float2 fa[8], fg[8];
+    #pragma unroll
+    for (int r = 0; r < 8; r++) {
+        fa[r] = make_float2(0.0f, 0.0f);
+        fg[r] = make_float2(0.0f, 0.0f);
+    }
+
+    stage_load(0);
+    stage_store(0);
+    // weights: a ring of GEMM_GROUPED_RING blocks per chain, RING - 1 loads
+    // in flight ahead of the MFMA. The chunk loop below is fully unrolled
+    // and a chunk is a multiple of the ring, so every ring index is a
+    // compile-time constant and the ring lives in registers (v2's note on
+    // ring arrays is about a runtime index). With v2's single block ahead a
+    // wave paid one memory latency per block: at MoE shapes few workgroups
+    // share a CU and nothing else hides it.
+    uint4 wa_ring[GEMM_GROUPED_RING], wg_ring[GEMM_GROUPED_RING];
+    __half swa_ring[GEMM_GROUPED_RING], swg_ring[GEMM_GROUPED_RING];
+    #pragma unroll
+    for (int i = 0; i < GEMM_GROUPED_RING; i++) {
+        wa_ring[i] = wg_ring[i] = make_uint4(0, 0, 0, 0);
+        swa_ring[i] = swg_ring[i] = __float2half(0.0f);
+        if (live && i < GEMM_GROUPED_RING - 1 && i < nb) {
+            wa_ring[i] = wrow_a[i];
+            swa_ring[i] = srow_a[i];
+            if constexpr (SWIGLU) {
+                wg_ring[i] = wrow_g[i];
+                swg_ring[i] = srow_g[i];
+            }
+        }
+    }
+    __syncthreads();
+
+    int buf = 0;
+    for (int jc = 0; jc < nb; jc += GEMM_V2_CHUNK, buf ^= 1) {
+        const int nblk = min(GEMM_V2_CHUNK, nb - jc);
+        const bool more = jc + GEMM_V2_CHUNK < nb;
+        if (more) stage_load(jc + GEMM_V2_CHUNK);
+        if (live) {
+            #pragma unroll
+            for (int jj = 0; jj < GEMM_V2_CHUNK; jj++) {
+                if (jj >= nblk) break;
+                const int j = jc + jj;
+                constexpr int R = GEMM_GROUPED_RING;
+                const uint4 wa = wa_ring[jj % R], wg = wg_ring[jj % R];
+                const float swa = __half2float(swa_ring[jj % R]);
+                const float swg = __half2float(swg_ring[jj % R]);
+                if (j + R - 1 < nb) {
+                    wa_ring[(jj + R - 1) % R] = wrow_a[j + R - 1];
+                    swa_ring[(jj + R - 1) % R] = srow_a[j + R - 1];
+                    if constexpr (SWIGLU) {
+                        wg_ring[(jj + R - 1) % R] = wrow_g[j + R - 1];
+                        swg_ring[(jj + R - 1) % R] = srow_g[j + R - 1];
+                    }
+                }
+                const v4i32_t a = *reinterpret_cast<const v4i32_t *>(
+                    &lds_a[buf][jj][lane & 31][khi * 16]);
+                v4i32_t b;
+                extract(wa, b);
+                v16i32_t ia = {}, ig = {};
+                ia = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, ia, 0, 0, 0);
+                if constexpr (SWIGLU) {
+                    extract(wg, b);
+                    ig = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, ig, 0, 0, 0);
+                }
+                #pragma unroll
+                for (int r2 = 0; r2 < 8; r2++) {
+                    const int col = ((2 * r2) & 3) + 8 * (r2 >> 1) + 4 * khi;
+                    const float2 sx2 = *reinterpret_cast<const float2 *>(
+                        &lds_s[buf][jj][col]);
+                    // single-lane ops: v2's float2 descale compiles to
+                    // packed f32 VALU ops, which this kernel keeps out
+                    fa[r2].x = fma_f32((float)ia[2 * r2], mul_f32(swa, sx2.x), fa[r2].x);
+                    fa[r2].y = fma_f32((float)ia[2 * r2 + 1], mul_f32(swa, sx2.y), fa[r2].y);
+                    if constexpr (SWIGLU) {
+                        fg[r2].x = fma_f32((float)ig[2 * r2], mul_f32(swg, sx2.x), fg[r2].x);
+                        fg[r2].y = fma_f32((float)ig[2 * r2 + 1], mul_f32(swg, sx2.y), fg[r2].y);
+                    }
+                }
+            }
+        }
+        if (more) stage_store(buf ^ 1);
+        __syncthreads();
+    }
+
+    if (!live) return;
+    const int m = mbase + mcol;
+    #pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int col = (r & 3) + 8 * (r >> 2) + 4 * khi;
+        const int slot = lds_slot[col];
+        const float av = (r & 1) ? fa[r >> 1].y : fa[r >> 1].x;
+        if constexpr (!SWIGLU) {
+            if (slot >= 0 && m < d) y[(int64_t)slot * d + m] = av;
+        } else {
+            // d % 32 == 0: every lane of a live wave holds a row, and the
+            // half-wave's 32 rows are Q80 block mbase / 32 of the slot
+            const float gv = (r & 1) ? fg[r >> 1].y : fg[r >> 1].x;
+            // silu or tanh-approx gelu, the expressions of k_swiglu_q80
+            const float act = EPI == GEPI_GELU
+                ? 0.5f * av * (1.0f + tanhf(0.797884560802865f * (av + 0.044715f * av * av * av)))
+                : av / (1.0f + __expf(-av));
+            const Q80Lane c = q80_quant_group32(act * gv);
+            const float bsum = group32_reduce_sum(c.qf);
+            if (slot >= 0) {
+                oq[(int64_t)slot * d + m] = (int8_t)c.qf;
+                if (mcol == 0) {
+                    os[(int64_t)slot * (d / QB) + mbase / QB] = c.d;
+                    obs[(int64_t)slot * (d / QB) + mbase / QB] = bsum;
+                }
+            }
+        }
+    }
+}
+
 // ============================================================== host bindings
 
 void q40_gemm(torch::Tensor qs, torch::Tensor scales, torch::Tensor xq,
@@ -293,7 +525,73 @@ void q40_gemm(torch::Tensor qs, torch::Tensor scales, torch::Tensor xq,
                            d, (int)batch, ksplit);
 }
 
+void q40_gemm_grouped(torch::Tensor qs, torch::Tensor scales, torch::Tensor xq,
+                      torch::Tensor xs, torch::Tensor plan, int64_t n_slots,
+                      int64_t k_slots,
+                      c10::optional<torch::Tensor> y = c10::nullopt,
+                      c10::optional<torch::Tensor> oq = c10::nullopt,
+                      c10::optional<torch::Tensor> os = c10::nullopt,
+                      c10::optional<torch::Tensor> obs = c10::nullopt,
+                      bool gelu = false) {
+    // qs [E, rows, n/2] stacked expert planes; plan from moe_group over the
+    // step's n_slots slots; slot s reads input row s / k_slots.
+    // y given: plain form, rows = d, y f32 [n_slots, d].
+    // oq/os/obs given: SwiGLU form, rows = 2 * ff (W1 over W3), the Q80
+    // triple [n_slots, ff] of act(w1 x) * (w3 x).
+    CHECK_CUDA(qs); CHECK_CONT(qs); CHECK_CONT(scales); CHECK_CONT(xq);
+    CHECK_CONT(xs); CHECK_CUDA(plan); CHECK_CONT(plan);
+    TORCH_CHECK(qs.dim() == 3, "grouped gemm takes stacked [E, rows, n/2] planes");
+    const bool swiglu = oq.has_value();
+    TORCH_CHECK(swiglu != y.has_value(), "pass y or the Q80 output triple");
+    TORCH_CHECK(!swiglu || (os.has_value() && obs.has_value()),
+                "the SwiGLU form writes oq, os and obs");
+    const int n_experts = qs.size(0);
+    const int rows = qs.size(1);
+    const int n = qs.size(2) * 2;
+    const int d = swiglu ? rows / 2 : rows;
+    TORCH_CHECK(n >= QB && n % QB == 0, "n must be a multiple of 32");
+    TORCH_CHECK(xq.size(-1) == n, "x width mismatch");
+    TORCH_CHECK(n_slots >= 1 && n_slots <= MOE_PLAN_MAX_SLOTS,
+                "grouped gemm supports 1..512 slots per step");
+    TORCH_CHECK(k_slots >= 1 && xq.size(0) * k_slots >= n_slots
+                && xs.numel() * QB >= xq.size(0) * (int64_t)n,
+                "input triple shorter than n_slots / k_slots rows");
+    TORCH_CHECK(plan.scalar_type() == torch::kInt32
+                && plan.numel() >= MOE_PLAN_INTS, "moe plan buffer too small");
+    const dim3 grid(ceil_div(d, 128), moe_max_tiles(n_experts, (int)n_slots));
+    auto launch = [&](auto k, float *yp, int8_t *qp, float *sp, float *bp) {
+        hipLaunchKernelGGL(k, grid, dim3(256), 0, cur_stream(),
+                           qs.data_ptr<uint8_t>(),
+                           reinterpret_cast<const __half *>(scales.data_ptr<at::Half>()),
+                           xq.data_ptr<int8_t>(), xs.data_ptr<float>(),
+                           plan.data_ptr<int>(), yp, qp, sp, bp, d, n,
+                           n_experts, (int)n_slots, (int)k_slots);
+    };
+    if (!swiglu) {
+        TORCH_CHECK(y->numel() >= n_slots * d, "y shorter than [n_slots, d]");
+        launch(k_q40_gemm_grouped<GEPI_PLAIN>, y->data_ptr<float>(), nullptr,
+               nullptr, nullptr);
+        return;
+    }
+    TORCH_CHECK(rows % 2 == 0 && d % QB == 0,
+                "the SwiGLU form needs ff % 32 == 0");
+    TORCH_CHECK(oq->numel() >= n_slots * d && os->numel() * QB >= n_slots * d
+                && obs->numel() * QB >= n_slots * d,
+                "Q80 output shorter than [n_slots, ff]");
+    if (gelu)
+        launch(k_q40_gemm_grouped<GEPI_GELU>, nullptr, oq->data_ptr<int8_t>(),
+               os->data_ptr<float>(), obs->data_ptr<float>());
+    else
+        launch(k_q40_gemm_grouped<GEPI_SILU>, nullptr, oq->data_ptr<int8_t>(),
+               os->data_ptr<float>(), obs->data_ptr<float>());
+}
+
 void register_gemm(py::module &m) {
+    m.def("q40_gemm_grouped", &q40_gemm_grouped, py::arg("qs"),
+          py::arg("scales"), py::arg("xq"), py::arg("xs"), py::arg("plan"),
+          py::arg("n_slots"), py::arg("k_slots"), py::arg("y") = py::none(),
+          py::arg("oq") = py::none(), py::arg("os") = py::none(),
+          py::arg("obs") = py::none(), py::arg("gelu") = false);
     m.def("q40_gemm", &q40_gemm, py::arg("qs"), py::arg("scales"),
           py::arg("xq"), py::arg("xs"), py::arg("y"), py::arg("batch"),
           py::arg("part") = py::none(), py::arg("variant") = -1);

@@ -110,6 +110,57 @@ __global__ void k_moe_gate(const float *__restrict__ logits,
         wts[(int64_t)b * topk + t] /= topsum;
 }
 
+// Routing plan of a multi-row MoE step (layout: dllama_common.h, "MoE
+// plan"): the step's slots sorted by (expert, slot) and cut into tiles of at
+// most 32 slots of one expert, the N dimension of k_q40_gemm_grouped. One
+// workgroup, one thread per slot. No atomics: slot s goes to its rank
+//   #{j : e_j < e_s} + #{j < s : e_j == e_s},
+// all-pairs over LDS as k_moe_gate ranks, so the plan is a pure function of
+// idx. A slot whose place within its expert is a multiple of 32 heads a tile;
+// a tile's index is the number of heads ranked before it. A top-k router
+// gives an expert at most NB <= 32 slots (one tile); any other idx just gets
+// more tiles, never more than moe_max_tiles. Expert ids are clamped into
+// 0..n_experts-1: the GEMM forms weight addresses from them.
+__global__ void __launch_bounds__(MOE_PLAN_MAX_SLOTS)
+k_moe_group(const int *__restrict__ idx, int *__restrict__ plan,
+            int n_slots, int n_experts, int max_tiles) {
+    __shared__ int se[MOE_PLAN_MAX_SLOTS];
+    __shared__ int shead[MOE_PLAN_MAX_SLOTS];  // rank of a tile head, else -1
+    const int s = threadIdx.x;                 // blockDim == MOE_PLAN_MAX_SLOTS
+    const bool have = s < n_slots;
+    const int e = have ? min(max(idx[s], 0), n_experts - 1) : 0;
+    if (have) se[s] = e;
+    __syncthreads();
+    int below = 0, before = 0, total = 0;
+    if (have) {
+        for (int j = 0; j < n_slots; j++) {
+            const int o = se[j];
+            below += o < e;
+            total += o == e;
+            before += (o == e) && j < s;
+        }
+    }
+    const int rank = below + before;
+    const bool head = have && before % MOE_TILE == 0;
+    if (have) plan[MOE_PLAN_PERM + rank] = s;
+    shead[s] = head ? rank : -1;
+    const int n_tiles = __syncthreads_count(head);
+    if (head) {
+        int t = 0;
+        for (int j = 0; j < n_slots; j++) {
+            const int r = shead[j];
+            t += r >= 0 && r < rank;
+        }
+        if (t < max_tiles) {
+            int *tile = plan + MOE_PLAN_TILES + 3 * t;
+            tile[0] = e;
+            tile[1] = rank;
+            tile[2] = min(MOE_TILE, total - before);
+        }
+    }
+    if (s == 0) plan[0] = min(n_tiles, max_tiles);
+}
+
 // weighted sum of expert outputs + residual fold + ssq (reference OP_SCALE +
 // OP_MERGE_SUM + merge_add fused): x[b] += sum_s wts[b,s] * y[b*k+s].
 // GATE=true recomputes the expert weights from the router logits in-kernel
@@ -245,6 +296,24 @@ void moe_gate(torch::Tensor logits, torch::Tensor idx, torch::Tensor wts,
                        wts.data_ptr<float>(), n_experts, (int)topk);
 }
 
+void moe_group(torch::Tensor idx, torch::Tensor plan, int64_t n_experts) {
+    // idx int32 [S] as moe_gate writes it (any values: ids are clamped and
+    // an expert with more than 32 slots is cut into several tiles)
+    CHECK_CUDA(idx); CHECK_CONT(idx); CHECK_CUDA(plan); CHECK_CONT(plan);
+    const int n_slots = (int)idx.numel();
+    TORCH_CHECK(idx.scalar_type() == torch::kInt32
+                && plan.scalar_type() == torch::kInt32, "moe_group takes int32");
+    TORCH_CHECK(n_slots >= 1 && n_slots <= MOE_PLAN_MAX_SLOTS,
+                "moe_group supports 1..512 slots per step");
+    TORCH_CHECK(n_experts >= 1 && n_experts <= 1024,
+                "moe_group supports <=1024 experts");
+    TORCH_CHECK(plan.numel() >= MOE_PLAN_INTS, "moe plan buffer too small");
+    hipLaunchKernelGGL(k_moe_group, dim3(1), dim3(MOE_PLAN_MAX_SLOTS), 0,
+                       cur_stream(), idx.data_ptr<int>(), plan.data_ptr<int>(),
+                       n_slots, (int)n_experts,
+                       moe_max_tiles((int)n_experts, n_slots));
+}
+
 void scale_merge_add(torch::Tensor x, torch::Tensor y, torch::Tensor wts,
                      torch::Tensor ssq, int64_t batch, int64_t topk,
                      bool gate = false) {
@@ -328,6 +397,7 @@ void scale_merge_pack(torch::Tensor y, torch::Tensor wts, torch::Tensor wire,
 void register_moe(py::module &m) {
     m.def("scale_merge_pack", &scale_merge_pack);
     m.def("moe_gate", &moe_gate);
+    m.def("moe_group", &moe_group);
     m.def("scale_merge_add", &scale_merge_add, py::arg("x"), py::arg("y"),
           py::arg("wts"), py::arg("ssq"), py::arg("batch"), py::arg("topk"),
           py::arg("gate") = false);
