@@ -298,6 +298,14 @@ class HipTransformer:
         # off, and min_rows has no crossover to come from: it keeps 8
         self.moe_gemm = flag("DLLAMA_MOE_GEMM", "0")
         self.moe_gemm_min_rows = 8
+        # dense matmuls of 8..32-row steps as one weight-streaming MFMA
+        # launch (q40_gemm_stream: whole-line weight reads, K split among a
+        # workgroup's waves, residual fold in the epilogue) instead of
+        # q40_gemm + reduce (+ add_ssq). Off by default: the pinned launch
+        # traces are the default lists (docs/DESIGN.md §12,
+        # profiles/r16_stream_gemm.md); set_stream_gemm on a live model
+        self.stream_gemm = flag("DLLAMA_GEMM_STREAM", "0")
+        self.stream_gemm_min_rows = 8  # where _mm leaves the GEMV
         # deferred-quant dense decode (EPI_RESID_Q + PRO2); =0 reverts to
         # explicit norm_quant launches
         self.use_deferred = flag("DLLAMA_DEFERRED", "1")
@@ -568,8 +576,11 @@ class HipTransformer:
 
     def _mm(self, lin: Linear, qb: QuantBuf, out, NB: int, amax=None):
         """Batched matmul dispatch: decode batches use the dot4 GEMV,
-        prefill batches (>=8) the int8-MFMA GEMM."""
-        if NB >= 8:
+        prefill batches (>=8) the int8-MFMA GEMM, or the weight-streaming
+        one where stream_gemm is on."""
+        if self.stream_gemm and NB >= self.stream_gemm_min_rows:
+            self.k.q40_gemm_stream(lin.qs, lin.scales, *qb.triple(), out, NB)
+        elif NB >= 8:
             self.k.q40_gemm(lin.qs, lin.scales, qb.q, qb.s, out, NB,
                             self.gemm_part)
         else:
@@ -671,6 +682,14 @@ class HipTransformer:
         self.moe_gemm = bool(on)
         self.graphs.clear()
 
+    def set_stream_gemm(self, on: bool = True):
+        """Dense matmuls of steps with at least stream_gemm_min_rows rows
+        take the weight-streaming MFMA GEMM (or stop taking it). Drops the
+        captured graphs: a step's graph holds one set of launches or the
+        other."""
+        self.stream_gemm = bool(on)
+        self.graphs.clear()
+
     def _swiglu_q80(self, out13, rows: int, qb: QuantBuf, *act):
         """act(w1 x) * (w3 x) over the fused W1|W3 output -> Q80 triple."""
         f = self.cfg.ff_dim0
@@ -719,6 +738,11 @@ class HipTransformer:
         if not self.tp_path and NB < 8:
             k.q40_gemv_resid(lin.qs, lin.scales, *qb.triple(),
                              self.x, self.ssq[slot], NB)
+            return
+        if (not self.tp_path and self.stream_gemm
+                and NB >= self.stream_gemm_min_rows):
+            k.q40_gemm_stream_resid(lin.qs, lin.scales, *qb.triple(),
+                                    self.x, self.ssq[slot], NB)
             return
         self._mm(lin, qb, self.partial, NB)
         if not self.tp_path:

@@ -485,6 +485,310 @@ k_q40_gemm_grouped(const uint8_t *__restrict__ qs,
     }
 }
 
+// ------------------------------------ weight-streaming GEMM (1..32-row steps)
+// The Q40xQ80 product for 1..32 activation rows as one launch that reads the
+// weights in whole cache lines (opt-in: DLLAMA_GEMM_STREAM, docs/DESIGN.md
+// §12). v_mfma_i32_16x16x32_i8 with the weights as the A operand: one MFMA
+// is 16 weight rows x 16 activation rows (columns) x one Q40 block, NT column
+// tiles share the A fragment. Fragment layout (tests/test_gemm_stream.py runs
+// asymmetric inputs through it): A lane = m + 16 g holds k-group g of row m,
+// B mirrored on the column, C register r of that lane is row 4 g + r of
+// column m. k-group g is block elements 4g..4g+3 and 16+4g..16+4g+3: the lo
+// and hi nibbles of dword g of the block, so the unpack is and / shift / and
+// and the nibbles stay unsigned. The -8 offset rides in as the MFMA's C
+// input, -8 * bsum[col][block], the same in a lane's four registers.
+//
+// Work split. A workgroup owns RT row tiles (16 or 32 weight rows), its W
+// waves split K in chunks of 8 blocks, contiguous chunk ranges per wave. Each
+// wave accumulates its slice in f32 (descale sw * sx rounded once, then one
+// fma per block, in block order), the W partial tiles are summed through LDS
+// in wave order, and the first RT * NT waves store the result: no K-split
+// across workgroups, no scratch buffer, no second launch. RT and W come from
+// (d, n) alone (stream_shape), so a row's bits depend neither on `batch` nor
+// on NT.
+//
+// Load path: through wave-private LDS tiles, not an in-register exchange.
+// A load instruction takes 8 weight rows x 8 blocks: 8 lanes hold the 8
+// consecutive 16-byte blocks of one row, one whole 128-byte line. The MFMA
+// wants dword g of block j of row m in lane m + 16 g, a 4 x 16 transpose of
+// dwords across all four 16-lane rows of the wave; permlane16/32 swaps move
+// whole rows pairwise and would need two swap rounds plus selects per block
+// per tile, against one ds_write_b128 per 8 blocks and one ds_read_b32 per
+// block here, and the same tile serves the activations: read directly in
+// fragment order they are 16 bytes of 16 different lines per load (16 tag
+// look-ups for 256 bytes), staged they are 256 contiguous bytes per 16 lanes.
+// The block index is XOR-swizzled with the row inside a tile so that both the
+// b128 writes and the b32 fragment reads touch every bank once. The tiles
+// are wave-private: a wave reads only what it wrote, in program order, so
+// the K loop has no barrier.
+//
+// Weights (the HBM stream) come through a 4-chunk register ring, issued
+// three chunks ahead; the chunk loop is unrolled by the ring so every ring
+// index is a compile-time constant. Activation codes, their scales and the
+// weight scales (L2 hits) are loaded one chunk ahead, before the ring's load
+// in program order, so waiting for them does not drain the ring.
+//
+// Activation bytes per weight byte, from L2: a chunk is RT * 2 KiB of
+// weights and min(batch, 16 NT) * 256 B of codes, i.e. batch / (8 RT):
+// 1 at 8 rows, 2 at 16 and 4 at 32 for RT = 1, half that for RT = 2.
+//
+// Edges: rows at or past d are clamped for loads and masked at the store;
+// columns at or past `batch` are staged as zero codes and form no address;
+// blocks at or past n / 32 are neither loaded nor multiplied.
+//
+// GS_PLAIN stores f32 y[b][row]; GS_RESID folds the residual like
+// q40_gemv_resid: x[b][row] += y and the squares into ssq_slot(b, blockIdx.x).
+enum { GS_PLAIN = 0, GS_RESID = 1 };
+#define GS_CHUNK 8
+#define GS_RING 4
+typedef uint4 __attribute__((may_alias)) gs_uint4;
+typedef uint2 __attribute__((may_alias)) gs_uint2;
+typedef float4 __attribute__((may_alias)) gs_float4;
+
+// dwords of LDS per wave: weight tile, code tile, weight scales, {sx, -8 bsum}
+static constexpr int gs_wave_dwords(int NT, int RT) {
+    return RT * 512 + NT * 1024 + RT * 128 + NT * 256;
+}
+
+__device__ __forceinline__ float add_f32(float a, float b) {
+    float r;
+    asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+template <int NT, int RT, int EPI>
+__global__ void __launch_bounds__(512)
+k_q40_gemm_stream(const uint8_t *__restrict__ qs,
+                  const __half *__restrict__ scales,
+                  const int8_t *__restrict__ xq,
+                  const float *__restrict__ xs,
+                  const float *__restrict__ xbs,
+                  float *__restrict__ y,    // GS_RESID: the residual x
+                  float *__restrict__ ssq,  // GS_RESID only
+                  int d, int n, int batch) {
+    extern __shared__ uint32_t gs_lds[];
+    constexpr int WD = gs_wave_dwords(NT, RT);
+    constexpr int R = GS_RING;
+    const int tid = threadIdx.x;
+    const int W = blockDim.x / WAVE;
+    const int wave = tid / WAVE;
+    const int lane = tid % WAVE;
+    const int m = lane & 15;   // fragment row (A) / column (B, C)
+    const int g = lane >> 4;   // k-group; C rows 4g..4g+3
+    const int lrow = lane >> 3;  // staging: row (or column) within 8
+    const int lblk = lane & 7;   // staging: block of the chunk
+    uint32_t *wl = gs_lds + wave * WD;
+    uint32_t *xl = wl + RT * 512;
+    float *swl = reinterpret_cast<float *>(xl + NT * 1024);
+    uint32_t *sbl = xl + NT * 1024 + RT * 128;
+
+    const int nb = n / QB;
+    const int nchunks = (nb + GS_CHUNK - 1) / GS_CHUNK;
+    const int c0 = nchunks * wave / W;
+    const int c1 = nchunks * (wave + 1) / W;
+    const int rbase = blockIdx.x * (RT * 16);
+
+    // staging addresses: load i takes rows rbase + 8 i .. + 7
+    const uint4 *wp[RT * 2];
+    const __half *sp[RT * 2];
+    int wst[RT * 2];
+    #pragma unroll
+    for (int i = 0; i < RT * 2; i++) {
+        const int row = min(rbase + i * 8 + lrow, d - 1);
+        wp[i] = reinterpret_cast<const uint4 *>(qs + (int64_t)row * (n >> 1)) + lblk;
+        sp[i] = scales + (int64_t)row * nb + lblk;
+        const int r16 = (i & 1) * 8 + lrow;
+        wst[i] = i * 256 + lrow * 32 + ((lblk ^ ((r16 >> 1) & 7)) << 2);
+    }
+    // codes: uint4 u of column 4 q + g (of tile nt), 16 uint4 per chunk row
+    const int xu = lane & 15;
+
+    uint4 wr[R][RT * 2];
+    uint4 xr[NT * 4];
+    __half swr[RT * 2];
+    float sxr[NT * 2], bsr[NT * 2];
+
+    auto load_w = [&](uint4 (&slot)[RT * 2], int c) {
+        const bool ok = c * GS_CHUNK + lblk < nb;
+        #pragma unroll
+        for (int i = 0; i < RT * 2; i++)
+            slot[i] = ok ? wp[i][c * GS_CHUNK] : make_uint4(0, 0, 0, 0);
+    };
+    auto load_x = [&](int c) {
+        const bool okb = c * GS_CHUNK + lblk < nb;
+        #pragma unroll
+        for (int i = 0; i < RT * 2; i++)
+            swr[i] = okb ? sp[i][c * GS_CHUNK] : __float2half(0.0f);
+        #pragma unroll
+        for (int i = 0; i < NT * 2; i++) {
+            const int col = i * 8 + lrow;
+            const bool ok = okb && col < batch;
+            const int64_t at = (int64_t)col * nb + c * GS_CHUNK + lblk;
+            sxr[i] = ok ? xs[at] : 0.0f;
+            bsr[i] = ok ? xbs[at] : 0.0f;
+        }
+        const bool oku = c * GS_CHUNK + (xu >> 1) < nb;
+        #pragma unroll
+        for (int i = 0; i < NT * 4; i++) {
+            const int col = (i >> 2) * 16 + (i & 3) * 4 + g;
+            xr[i] = make_uint4(0, 0, 0, 0);
+            if (oku && col < batch)
+                xr[i] = *reinterpret_cast<const uint4 *>(
+                    xq + (int64_t)col * n + (int64_t)c * (GS_CHUNK * QB) + xu * 16);
+        }
+    };
+    auto stage = [&](const uint4 (&slot)[RT * 2]) {
+        #pragma unroll
+        for (int i = 0; i < RT * 2; i++) {
+            *reinterpret_cast<gs_uint4 *>(wl + wst[i]) = slot[i];
+            swl[lblk * (RT * 16) + i * 8 + lrow] = __half2float(swr[i]);
+        }
+        #pragma unroll
+        for (int i = 0; i < NT * 2; i++) {
+            const int col = i * 8 + lrow;
+            // the code sum is an integer below 2^24: exact in f32 and in int
+            *reinterpret_cast<gs_uint2 *>(sbl + (lblk * (NT * 16) + col) * 2) =
+                make_uint2(__float_as_uint(sxr[i]), (uint32_t)(-8 * (int)bsr[i]));
+        }
+        #pragma unroll
+        for (int i = 0; i < NT * 4; i++) {
+            const int c16 = (i & 3) * 4 + g;
+            *reinterpret_cast<gs_uint4 *>(
+                xl + (i >> 2) * 1024 + c16 * 64 + ((xu ^ c16) << 2)) = xr[i];
+        }
+    };
+
+    float acc[RT][NT][4];
+    #pragma unroll
+    for (int a = 0; a < RT; a++)
+        #pragma unroll
+        for (int b = 0; b < NT; b++)
+            #pragma unroll
+            for (int r = 0; r < 4; r++) acc[a][b][r] = 0.0f;
+
+    if (c0 < c1) load_x(c0);
+    #pragma unroll
+    for (int i = 0; i < R - 1; i++) {
+        if (c0 + i < c1) load_w(wr[i], c0 + i);
+    }
+
+    const int wrd = m * 32 + g;            // weight fragment read, + swizzled block
+    const int wsw = (m >> 1) & 7;
+    const int xrd = m * 64 + g;            // code fragment read
+    auto block = [&](int jj) {
+        long a[RT];
+        gs_float4 sw4[RT];
+        #pragma unroll
+        for (int t = 0; t < RT; t++) {
+            const uint32_t v = wl[t * 512 + wrd + ((jj ^ wsw) << 2)];
+            const uint32_t lo = v & 0x0F0F0F0Fu;
+            const uint32_t hi = (v >> 4) & 0x0F0F0F0Fu;
+            a[t] = (long)(((uint64_t)hi << 32) | lo);
+            sw4[t] = *reinterpret_cast<const gs_float4 *>(
+                swl + jj * (RT * 16) + t * 16 + 4 * g);
+        }
+        #pragma unroll
+        for (int u = 0; u < NT; u++) {
+            const uint32_t x0 = xl[u * 1024 + xrd + (((2 * jj) ^ m) << 2)];
+            const uint32_t x1 = xl[u * 1024 + xrd + (((2 * jj + 1) ^ m) << 2)];
+            const long b = (long)(((uint64_t)x1 << 32) | x0);
+            const gs_uint2 sb = *reinterpret_cast<const gs_uint2 *>(
+                sbl + (jj * (NT * 16) + u * 16 + m) * 2);
+            const float sx = __uint_as_float(sb.x);
+            const int off = (int)sb.y;
+            #pragma unroll
+            for (int t = 0; t < RT; t++) {
+                v4i32_t ci = {off, off, off, off};
+                ci = __builtin_amdgcn_mfma_i32_16x16x32_i8(a[t], b, ci, 0, 0, 0);
+                const float s4[4] = {sw4[t].x, sw4[t].y, sw4[t].z, sw4[t].w};
+                #pragma unroll
+                for (int r = 0; r < 4; r++)
+                    acc[t][u][r] = fma_f32((float)ci[r], mul_f32(s4[r], sx),
+                                           acc[t][u][r]);
+            }
+        }
+    };
+    for (int cb = c0; cb < c1; cb += R) {
+        #pragma unroll
+        for (int ii = 0; ii < R; ii++) {
+            const int c = cb + ii;
+            if (c >= c1) break;  // wave-uniform
+            stage(wr[ii]);
+            if (c + 1 < c1) load_x(c + 1);
+            if (c + R - 1 < c1) load_w(wr[(ii + R - 1) % R], c + R - 1);
+            const int nblk = min(GS_CHUNK, nb - c * GS_CHUNK);
+            // a whole chunk runs as straight-line code, so the scheduler
+            // overlaps the blocks' LDS reads, MFMAs and descales (in two
+            // halves for the 4-tile form, which spilled as one)
+            if (nblk == GS_CHUNK) {
+                constexpr int UN = RT * NT == 4 ? GS_CHUNK / 2 : GS_CHUNK;
+                #pragma unroll 1
+                for (int j0 = 0; j0 < GS_CHUNK; j0 += UN) {
+                    #pragma unroll
+                    for (int q = 0; q < UN; q++) block(j0 + q);
+                }
+            } else {
+                #pragma unroll 1
+                for (int jj = 0; jj < nblk; jj++) block(jj);
+            }
+        }
+    }
+
+    // the W partial tiles, summed in wave order by the first RT * NT waves
+    __syncthreads();
+    gs_float4 *red = reinterpret_cast<gs_float4 *>(gs_lds);
+    #pragma unroll
+    for (int t = 0; t < RT; t++)
+        #pragma unroll
+        for (int u = 0; u < NT; u++)
+            red[(wave * (RT * NT) + t * NT + u) * WAVE + lane] =
+                make_float4(acc[t][u][0], acc[t][u][1], acc[t][u][2], acc[t][u][3]);
+    __syncthreads();
+    float sq = 0.0f;
+    if (wave < RT * NT) {
+        float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int w = 0; w < W; w++) {
+            const gs_float4 p = red[(w * (RT * NT) + wave) * WAVE + lane];
+            s[0] = add_f32(s[0], p.x);
+            s[1] = add_f32(s[1], p.y);
+            s[2] = add_f32(s[2], p.z);
+            s[3] = add_f32(s[3], p.w);
+        }
+        const int col = (wave % NT) * 16 + m;
+        const int row0 = rbase + (wave / NT) * 16 + 4 * g;
+        if (col < batch) {
+            #pragma unroll
+            for (int r = 0; r < 4; r++) {
+                if (row0 + r >= d) continue;
+                float *at = y + (int64_t)col * d + row0 + r;
+                if constexpr (EPI == GS_PLAIN) {
+                    *at = s[r];
+                } else {
+                    const float xv = add_f32(*at, s[r]);
+                    *at = xv;
+                    sq = fma_f32(xv, xv, sq);
+                }
+            }
+        }
+    }
+    if constexpr (EPI == GS_RESID) {
+        // a column's squares: over the 4 k-groups by shuffle, over the RT row
+        // tiles through LDS (past the partial tiles), one atomic per column
+        float *sql = reinterpret_cast<float *>(gs_lds) + W * (RT * NT) * 256;
+        sq += __shfl_xor(sq, 16, WAVE);
+        sq += __shfl_xor(sq, 32, WAVE);
+        if (wave < RT * NT && lane < 16) sql[wave * 16 + lane] = sq;
+        __syncthreads();
+        if (tid < NT * 16 && tid < batch) {
+            float t = 0.0f;
+            #pragma unroll
+            for (int a = 0; a < RT; a++)
+                t += sql[(a * NT + (tid >> 4)) * 16 + (tid & 15)];
+            atomicAdd(ssq_slot(ssq, tid, blockIdx.x), t);
+        }
+    }
+}
+
 // ============================================================== host bindings
 
 void q40_gemm(torch::Tensor qs, torch::Tensor scales, torch::Tensor xq,
@@ -586,7 +890,108 @@ void q40_gemm_grouped(torch::Tensor qs, torch::Tensor scales, torch::Tensor xq,
                os->data_ptr<float>(), obs->data_ptr<float>());
 }
 
+// Rows per workgroup (16 or 32) and K-splitting waves (4 or 8) of the stream
+// GEMM over a [d, n] matrix, from (d, n) alone so that a row's summation
+// order does not depend on the batch. Measured with `tools/kernel_bench.py
+// stream --sweep` at the 8B shapes (profiles/r16_stream_gemm.md): 16-row
+// workgroups win at d = 4096 (wo, w2: 256 workgroups of 8 waves, two waves
+// on every SIMD of 256 CUs), 32-row ones from d = 6144 up; 8 K-splitting
+// waves win while the grid has at most two workgroups per CU, 4 above that
+// (w13, wcls), and a wave is not given less than a chunk of 8 blocks.
+// `rows` / `waves` override the rule: that is how the sweep runs.
+struct StreamShape { int rt, waves; };
+
+static StreamShape stream_shape(int d, int n, int rows, int waves) {
+    StreamShape s;
+    s.rt = rows ? rows / 16 : (d >= 6144 ? 2 : 1);
+    const bool few = ceil_div(d, s.rt * 16) <= 512;
+    s.waves = waves ? waves
+        : (few && ceil_div(n / QB, GS_CHUNK) >= 8 ? 8 : 4);
+    return s;
+}
+
+template <int NT, int RT, int EPI>
+static void stream_launch(const StreamShape &s, const uint8_t *qs, const __half *sc,
+                          const int8_t *xq, const float *xs, const float *xbs,
+                          float *y, float *ssq, int d, int n, int batch) {
+    auto *kern = k_q40_gemm_stream<NT, RT, EPI>;
+    // 8 waves of the largest form stage 120 KiB, above the default cap
+    static const hipError_t attr = hipFuncSetAttribute(
+        reinterpret_cast<const void *>(kern),
+        hipFuncAttributeMaxDynamicSharedMemorySize,
+        8 * gs_wave_dwords(NT, RT) * 4);
+    TORCH_CHECK(attr == hipSuccess, "stream gemm: LDS attribute: ",
+                hipGetErrorString(attr));
+    const size_t lds = (size_t)s.waves * gs_wave_dwords(NT, RT) * 4;
+    hipLaunchKernelGGL(kern, dim3(ceil_div(d, RT * 16)), dim3(s.waves * WAVE),
+                       lds, cur_stream(), qs, sc, xq, xs, xbs, y, ssq, d, n, batch);
+}
+
+template <int EPI>
+static void stream_dispatch(torch::Tensor &qs, torch::Tensor &scales,
+                            torch::Tensor &xq, torch::Tensor &xs,
+                            torch::Tensor &xbs, torch::Tensor &y, float *ssq,
+                            int64_t batch, int64_t rows, int64_t waves) {
+    CHECK_CUDA(qs); CHECK_CONT(qs); CHECK_CONT(scales); CHECK_CONT(xq);
+    CHECK_CONT(xs); CHECK_CONT(xbs); CHECK_CUDA(y); CHECK_CONT(y);
+    const int d = qs.size(0);
+    const int n = qs.size(1) * 2;
+    TORCH_CHECK(d >= 1 && n >= QB && n % QB == 0, "n must be a multiple of 32");
+    TORCH_CHECK(batch >= 1 && batch <= 32, "stream gemm takes 1..32 rows");
+    TORCH_CHECK(xq.size(-1) == n && xq.numel() >= batch * n
+                && xs.numel() * QB >= batch * n && xbs.numel() * QB >= batch * n,
+                "input triple shorter than [batch, n]");
+    TORCH_CHECK(xs.scalar_type() == torch::kFloat32
+                && xbs.scalar_type() == torch::kFloat32
+                && y.scalar_type() == torch::kFloat32, "xs, xbs and y are f32");
+    TORCH_CHECK(y.numel() >= batch * d, "output shorter than [batch, d]");
+    TORCH_CHECK((rows == 0 || rows == 16 || rows == 32)
+                && (waves == 0 || waves == 4 || waves == 8),
+                "stream gemm: rows 0/16/32, waves 0/4/8");
+    const StreamShape s = stream_shape(d, n, (int)rows, (int)waves);
+    auto go = [&](auto launch) {
+        launch(s, qs.data_ptr<uint8_t>(),
+               reinterpret_cast<const __half *>(scales.data_ptr<at::Half>()),
+               xq.data_ptr<int8_t>(), xs.data_ptr<float>(), xbs.data_ptr<float>(),
+               y.data_ptr<float>(), ssq, d, n, (int)batch);
+    };
+    if (batch <= 16) {
+        if (s.rt == 1) go(stream_launch<1, 1, EPI>);
+        else go(stream_launch<1, 2, EPI>);
+    } else {
+        if (s.rt == 1) go(stream_launch<2, 1, EPI>);
+        else go(stream_launch<2, 2, EPI>);
+    }
+}
+
+void q40_gemm_stream(torch::Tensor qs, torch::Tensor scales, torch::Tensor xq,
+                     torch::Tensor xs, torch::Tensor xbs, torch::Tensor y,
+                     int64_t batch, int64_t rows = 0, int64_t waves = 0) {
+    // y f32 [batch, d] = the Q40 x Q80 product of the first `batch` rows
+    stream_dispatch<GS_PLAIN>(qs, scales, xq, xs, xbs, y, nullptr, batch, rows, waves);
+}
+
+void q40_gemm_stream_resid(torch::Tensor qs, torch::Tensor scales,
+                           torch::Tensor xq, torch::Tensor xs, torch::Tensor xbs,
+                           torch::Tensor x, torch::Tensor ssq, int64_t batch,
+                           int64_t rows = 0, int64_t waves = 0) {
+    // x[b] += product, the rows' squares into ssq's spread slots
+    CHECK_CUDA(ssq); CHECK_CONT(ssq);
+    TORCH_CHECK(ssq.scalar_type() == torch::kFloat32
+                && ssq.numel() >= batch * SSQ_SPREAD * SSQ_PAD,
+                "ssq shorter than `batch` rows of spread slots");
+    stream_dispatch<GS_RESID>(qs, scales, xq, xs, xbs, x, ssq.data_ptr<float>(),
+                              batch, rows, waves);
+}
+
 void register_gemm(py::module &m) {
+    m.def("q40_gemm_stream", &q40_gemm_stream, py::arg("qs"), py::arg("scales"),
+          py::arg("xq"), py::arg("xs"), py::arg("xbs"), py::arg("y"),
+          py::arg("batch"), py::arg("rows") = 0, py::arg("waves") = 0);
+    m.def("q40_gemm_stream_resid", &q40_gemm_stream_resid, py::arg("qs"),
+          py::arg("scales"), py::arg("xq"), py::arg("xs"), py::arg("xbs"),
+          py::arg("x"), py::arg("ssq"), py::arg("batch"), py::arg("rows") = 0,
+          py::arg("waves") = 0);
     m.def("q40_gemm_grouped", &q40_gemm_grouped, py::arg("qs"),
           py::arg("scales"), py::arg("xq"), py::arg("xs"), py::arg("plan"),
           py::arg("n_slots"), py::arg("k_slots"), py::arg("y") = py::none(),

@@ -83,7 +83,13 @@ def init_dist_comm(backend: str | None = None, timeout_s: int = 300) -> Comm:
     if world == 1:
         return SingleComm()
     if backend is None:
-        backend = "nccl" if torch.cuda.is_available() else "gloo"
+        # one process per GPU: with fewer GPUs than local ranks (a CPU-mode
+        # run of several ranks on a one-GPU box) there is no device to bind
+        # every rank to, and the ranks' tensors are host tensors: gloo
+        local_world = int(os.environ.get("LOCAL_WORLD_SIZE", "1"))
+        on_gpus = (torch.cuda.is_available()
+                   and torch.cuda.device_count() >= local_world)
+        backend = "nccl" if on_gpus else "gloo"
     if backend == "nccl":
         # bind the device BEFORE init so the first collective (and barrier's
         # device guess) never lands every rank on GPU 0

@@ -18,8 +18,10 @@ model steps rows only). --context N starts the timed decode at position N:
 the prompt is still --prefill tokens, the cache rows between hold zeros, and
 every step reads all N of them, so long contexts are timed without paying
 B long prefills. --kv-dtype q80 runs either form on the Q80 KV cache.
---logprobs turns set_logprobs on: every step also computes the rows' token
-log-probabilities (top 20) in the graph and copies them back with the tokens.
+--stream-gemm on|ab runs the row steps with set_stream_gemm (ab: off and on
+alternately, three times each, per B). --logprobs turns set_logprobs on:
+every step also computes the rows' token log-probabilities (top 20) in the
+graph and copies them back with the tokens.
 
 Warmup and timing follow bench.py: untimed warmup steps on the shapes of
 the timed window, then a host clock around `--steps` steps ending in a
@@ -61,6 +63,9 @@ def main():
                     help="KV cache format (default: the model's, f16)")
     ap.add_argument("--logprobs", action="store_true",
                     help="set_logprobs(True): log-probabilities in every step")
+    ap.add_argument("--stream-gemm", default="off", choices=["off", "on", "ab"],
+                    help="set_stream_gemm: off, on, or ab = every B timed "
+                         "off and on alternately, three times each")
     args = ap.parse_args()
     context = max(args.context, args.prefill)
     if not torch.cuda.is_available():
@@ -114,8 +119,7 @@ def main():
         return {"tokens_per_s": round(B * args.steps / elapsed, 2),
                 "ms_per_step": round(elapsed / args.steps * 1000.0, 4)}
 
-    rows = {}
-    for B in batches:
+    def measure(B):
         slots = list(range(B))
         if args.kv_pages:
             for s in range(model.n_slots):
@@ -140,8 +144,21 @@ def main():
         elapsed = timed(step)
         assert model.graphs.get(("rows", B, model.logprobs)) is not None, \
             "the timed steps were not graph replays"
-        rows[str(B)] = entry(elapsed, B)
+        return entry(elapsed, B)
+
+    rows = {}
+    for B in batches:
+        if args.stream_gemm != "ab":
+            model.set_stream_gemm(args.stream_gemm == "on")
+            rows[str(B)] = measure(B)
+        else:
+            rows[str(B)] = {"off": [], "on": []}
+            for _ in range(3):
+                for name in ("off", "on"):
+                    model.set_stream_gemm(name == "on")
+                    rows[str(B)][name].append(measure(B))
         print(f"# B={B}: {rows[str(B)]}", file=sys.stderr)
+    model.set_stream_gemm(args.stream_gemm == "on")
 
     # the single-sequence path, same loop shape: forward_sample replays the
     # deferred-quant decode graph with the sampler inside
@@ -179,6 +196,7 @@ def main():
                    "kv_cache_bytes": model.kv_cache_bytes(),
                    "sampling": "on device, temperature 0",
                    "logprobs": args.logprobs,
+                   "stream_gemm": args.stream_gemm,
                    "data": "synthetic (random-init weights, random prompt)"},
     }))
 

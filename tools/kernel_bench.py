@@ -264,6 +264,71 @@ def resid_ab(rounds=5, forms=(16, 8, 4)):
         del qs, sc
 
 
+def stream_ab(rounds=3, batches=(8, 16, 32), sweep=False):
+    """q40_gemm_stream against the launches it replaces, alone in an isolated
+    hipGraph at the 8B shapes, NB rows: `parent` is q40_gemm with its K-split
+    reduce, plus add_ssq on the down-projections (wo, w2), where `stream` is
+    q40_gemm_stream_resid. The graph rotates over weight copies that together
+    exceed 300 MB (see resid_ab), the candidates are interleaved over
+    `rounds`; median us per call and the stream's weight bytes/s against the
+    6.3 TB/s ceiling. --sweep adds every (rows, waves) work split of the
+    stream kernel, the measurement stream_shape()'s rule comes from.
+
+      python tools/kernel_bench.py stream [--sweep]"""
+    part = torch.zeros(32 * 32 * 8192, device=dev)
+    print("\n-- q40_gemm_stream vs q40_gemm (+reduce, +add_ssq), isolated graph, "
+          "rotating >300 MB of weights (median us per call) --")
+    for tag, d, n, resid in (("wo", 4096, 4096, True), ("w2", 4096, 14336, True),
+                             ("qkv", 6144, 4096, False), ("w13", 28672, 4096, False),
+                             ("cls", 128256, 4096, False)):
+        nbytes = d * n * 0.5625
+        copies = int(300e6 // nbytes) + 1
+        qs = torch.randint(0, 256, (copies, d, n // 2), dtype=torch.uint8,
+                           device=dev, generator=g)
+        sc = (torch.rand((copies, d, n // 32), device=dev, generator=g)
+              * 0.01).to(torch.float16)
+        xq, xs, xbs = mkx(32, n)
+        y = torch.zeros(32, d, device=dev)
+        xr = torch.zeros(32, d, device=dev)
+        sq = torch.zeros(32, 16 * 32, device=dev)
+        it = [0]
+
+        def parent(B):
+            i = it[0] % copies
+            it[0] += 1
+            k.q40_gemm(qs[i], sc[i], xq, xs, y, B, part)
+            if resid:
+                k.add_ssq(xr[:B], y[:B], sq, B)
+
+        def stream(B, rows=0, waves=0):
+            i = it[0] % copies
+            it[0] += 1
+            if resid:
+                k.q40_gemm_stream_resid(qs[i], sc[i], xq, xs, xbs, xr, sq, B,
+                                        rows, waves)
+            else:
+                k.q40_gemm_stream(qs[i], sc[i], xq, xs, xbs, y, B, rows, waves)
+
+        for B in batches:
+            cands = {"parent": lambda: parent(B), "stream": lambda: stream(B)}
+            if sweep:
+                for rows in (16, 32):
+                    for waves in (4, 8):
+                        cands[f"{rows}r{waves}w"] = (
+                            lambda r=rows, w=waves: stream(B, r, w))
+            t = {name: [] for name in cands}
+            for _ in range(rounds):
+                for name, fn in cands.items():
+                    it[0] = 0
+                    t[name].append(bench(fn, n=max(16, copies), reps=3))
+            med = {name: statistics.median(v) for name, v in t.items()}
+            print(f"{tag:4s} {d:6d}x{n:<5d} NB={B:2d}  " + "  ".join(
+                f"{name}: {v:7.2f}" for name, v in med.items())
+                + f"  stream {nbytes / med['stream'] / 1e6:5.2f} TB/s"
+                f" ({100 * nbytes / med['stream'] / 6.3e6:3.0f}% of 6.3)")
+        del qs, sc
+
+
 if sys.argv[1:] == ["attn"]:
     attn_ab()
     sys.exit(0)
@@ -299,6 +364,10 @@ def mkx(nb, n):
     s = torch.rand(nb, n // 32, device=dev, generator=g) * 0.01
     bs = torch.rand(nb, n // 32, device=dev, generator=g)
     return q, s, bs
+
+if sys.argv[1:2] == ["stream"]:
+    stream_ab(sweep="--sweep" in sys.argv[2:])
+    sys.exit(0)
 
 NB = 1
 dim, ffd, qkvd = 4096, 14336, 6144

@@ -6,6 +6,8 @@ captures, which the switch drops: the same cost in both settings), and the
 tok/s of the last 512 tokens alone, where the context is longest.
 
   python tools/prefill_probe.py [lengths...]      default 512 2048 8192
+    --ab stream                alternate set_stream_gemm instead (chunk attention
+                               stays off): the weight-streaming GEMM
     --kv-dtype q80             a Q80 KV cache; "on" is set_chunk_attn(True, q80=True)
     --kv-pages M --page-size P a paged cache: the prompt goes through
                                forward_rows into slot 0, whose pages are mapped
@@ -18,6 +20,7 @@ from dllama_amd.models.hip_model import HipTransformer
 
 ap = argparse.ArgumentParser()
 ap.add_argument("lengths", type=int, nargs="*", default=[512, 2048, 8192])
+ap.add_argument("--ab", choices=("chunk", "stream"), default="chunk")
 ap.add_argument("--kv-dtype", choices=("f16", "q80"), default="f16")
 ap.add_argument("--kv-pages", type=int, default=0)
 ap.add_argument("--page-size", type=int, default=64)
@@ -59,8 +62,12 @@ def prefill(n):
 for n in lengths:
     for rep in range(3):
         for on in (False, True):
-            m.set_chunk_attn(on, q80=q80)
+            if a.ab == "stream":
+                m.set_stream_gemm(on)
+            else:
+                m.set_chunk_attn(on, q80=q80)
             dt, tail = prefill(n)
-            print(f"prefill {n:5d} tokens, chunk attn {'on ' if on else 'off'}: "
+            what = "stream gemm" if a.ab == "stream" else "chunk attn"
+            print(f"prefill {n:5d} tokens, {what} {'on ' if on else 'off'}: "
                   f"{dt*1000:8.1f} ms = {n/dt:6.0f} tok/s; last 512: "
                   f"{512/tail:6.0f} tok/s", flush=True)
