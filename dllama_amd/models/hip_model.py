@@ -155,6 +155,8 @@ class KVAddr:
         # with the row table; None = the step launches what it always did
         self.attn_chunk = "attn_chunk" + suffix
         self.chunk = None
+        # the GQA-packed MFMA decode attention (set_gqa_attn)
+        self.attn_gqa = "attn_gqa" + suffix
 
 
 class HipTransformer:
@@ -283,6 +285,21 @@ class HipTransformer:
         self.chunk_attn = env.get("DLLAMA_ATTN_CHUNK", "0") in ("1", "2")
         self.chunk_attn_q80 = env.get("DLLAMA_ATTN_CHUNK", "0") == "2"
         self.chunk_min_rows = 8  # where the matmuls switch to the GEMM
+        # decode rows on the matrix cores: steps above the wide tier that the
+        # chunk kernel does not take run k_attn_gqa (the kv_mul query heads
+        # of a KV head are the MFMA N dimension, K/V read once per KV head
+        # and row) instead of k_attn_split, for an f16 cache. Off by default
+        # (docs/DESIGN.md §13); set_gqa_attn on a live model
+        self.gqa_attn = flag("DLLAMA_ATTN_GQA", "0")
+        # a single-sequence decode step below this position keeps the split
+        # pair: one row at S=16 is too little work for the MFMA kernel (12.3
+        # against 9.9 us at position 512, 18.3 against 23.7 at 2048, the
+        # first measured position where it wins and an S boundary, so the
+        # decode graph is recaptured there anyway). Row steps take the kernel
+        # at every position above the wide tier: from 8 rows it won wherever
+        # it was measured (profiles/r17_gqa_decode_attention.md)
+        self.gqa_min_pos = 2048
+        self._gqa_pos_ok = True  # the last _pick_splits: at or above it
         # the S in force above the wide tier, put back when a step leaves it
         self._splits_above = self.attn_splits if self.attn_splits != 1 else 8
         # measured-slower fusions kept for shape experiments (profiles r02):
@@ -640,12 +657,35 @@ class HipTransformer:
                 *(self.zq.triple() if emit_q80 else ()),
                 **self._kv_scales(l))
             return
+        if self._gqa_step():
+            getattr(self.k, addr.attn_gqa)(
+                self.qkv_out, self.qkv_ld, self.k_cache[l], self.v_cache[l],
+                self.zbuf[:B], *addr.where, B, c.n_heads0, self.kv_mul,
+                c.head_dim, self.attn_splits, self.attn_ml, self.attn_o,
+                *(self.zq.triple() if emit_q80 else ()))
+            return
         getattr(self.k, addr.attn)(
             self.qkv_out, self.qkv_ld, self.k_cache[l], self.v_cache[l],
             self.zbuf[:B], *addr.where, B, c.n_heads0, self.kv_mul,
             c.head_dim, self.attn_splits, self.attn_ml, self.attn_o,
             *addr.attn_scratch, *(self.zq.triple() if emit_q80 else ()),
             **self._kv_scales(l))
+
+    def _gqa_step(self) -> bool:
+        """A step the chunk kernel left takes the GQA-packed MFMA attention:
+        the option is on, the cache is f16, the kernel has an instantiation
+        for the heads, the step is above the wide tier (S > 1) and, for a
+        single sequence, at or above gqa_min_pos."""
+        return bool(self.gqa_attn and self.kv_dtype == "f16"
+                    and self.cfg.head_dim in (64, 128) and self.kv_mul <= 16
+                    and self.attn_splits > 1 and self._gqa_pos_ok)
+
+    def set_gqa_attn(self, on: bool = True):
+        """Decode rows above the wide tier take the GQA-packed MFMA attention
+        (or stop taking it). Drops the captured graphs: a step's graph holds
+        one kernel or the other."""
+        self.gqa_attn = bool(on)
+        self.graphs.clear()
 
     def _chunk_step(self, B: int, addr: KVAddr):
         """The chunk attention's extra arguments if this step takes it, else
@@ -1522,6 +1562,7 @@ class HipTransformer:
         # and skips the wide tier; S=1 is never handed to the pair there.
         # set_wide_rows turns the tier on for row steps: BatchEngine calls
         # it.
+        self._gqa_pos_ok = rows or pos >= self.gqa_min_pos
         if not self.adaptive_thresh:
             return self.attn_splits
         if ((self.wide_rows or not rows)

@@ -1061,6 +1061,313 @@ k_attn_chunk(const float *__restrict__ q, int q_ld,
     }
 }
 
+// ------------------------------------------------- GQA-packed MFMA decode
+// The decode-row producer of the split scratch: a decode row is a run of one,
+// so what a workgroup can share is the kv_mul query heads of a KV head. They
+// are the N dimension of the MFMA, and K/V is read once per (KV head, row)
+// instead of once per query head. Grid (n_kv_heads0, B, S), 4 waves; nothing
+// in it depends on positions. Split sp walks the 32-timestep tiles sp, sp+S,
+// .. up to the tile that holds the row's position, and wave w takes every
+// fourth of them: the waves split time (k_attn_chunk's split heads), each
+// carries (m, l, O) of all heads, and they merge through LDS in wave order at
+// the end. No barrier inside the timestep loop.
+//
+// Layouts (v_mfma_f32_16x16x32_f16): A[m][k] and B[k][n] hold k = 8*(lane>>4)
+// + j in half j of lane (m or n) + 16*(lane>>4); C[m][n] holds n = lane&15,
+// m = 4*(lane>>4) + r in register r. Scores are computed transposed,
+// S^T = K Q^T (m = timestep, n = query head): the A fragment of a K row is 8
+// consecutive halves of the cache row, one 16-byte load and no LDS, and a
+// lane holds 4 scores of ONE head per 16-timestep half of the tile. The
+// online softmax of a head is lane-local but for the exchanges with lane^16
+// and lane^32. The lane's 8 weights of a tile, rounded to f16, are directly
+// the B operand of O^T += V^T P^T over the timesteps
+//   t(g, j) = 16*(j>>2) + 4*g + (j&3),  g = lane>>4, j = 0..7,
+// because the MFMA only sums over k: the A operand V^T gathers the same
+// timesteps. P never moves between lanes; O^T again holds the lane's head.
+//
+// V is d-contiguous in the cache and the A operand wants 8 timesteps of one
+// d per lane. It goes through a wave-private LDS tile: lane (g, dc) loads the
+// 8-element chunk dc of the rows t(g, 0..7) (whole 128- or 256-byte row
+// pieces per 16 lanes), transposes its 8x8 halves in registers and stores
+// one vector per d, so that row d of the tile holds the 32 timesteps in k
+// order and a fragment is one 16-byte LDS read. A wave reads only what it
+// wrote, in program order: no barrier. (head_dim 64 has 8 chunks per row:
+// a lane takes half of the k group, 4 timesteps, and stores 8 bytes per d.)
+//
+// Prefetch: K and V of a wave's next tile are loaded into the other of two
+// register sets before the current tile is multiplied (the loop is unrolled
+// by the two sets), page ids one tile further ahead. Loads are never guarded:
+// a timestep past the row's position re-reads the row of the position itself,
+// in the last tile (masked: its weight is 0 by name) and in the one prefetch
+// past it (never used), so no address past the position is formed and no
+// unmapped page is looked up.
+//
+// Rounding points are k_attn_chunk's: q*scale (f32) -> f16 once, P -> f16
+// per tile; scores, m, l and O accumulate in f32.
+typedef float v4f_t __attribute__((ext_vector_type(4)));
+
+constexpr int GQA_T = 32;      // timesteps per tile = MFMA K of O^T += V^T P^T
+constexpr int GQA_HEADS = 16;  // query heads per KV head served = MFMA N
+constexpr int GQA_NW = 4;      // waves per workgroup
+constexpr int GQA_VLD = GQA_T + 8;  // halves per V^T row: 16-byte rows, skewed
+
+template <int VEC, typename KVT, typename ROWS>
+__global__ void __launch_bounds__(GQA_NW * WAVE, 2)
+k_attn_gqa(const float *__restrict__ q, int q_ld,
+           const KVT *__restrict__ kc_all, const KVT *__restrict__ vc_all,
+           const ROWS rows, int n_heads0, int kv_mul, int kv_dim0, float scale,
+           float *__restrict__ ml_scratch, float *__restrict__ o_scratch) {
+    static_assert(std::is_same_v<KVT, __half>, "k_attn_gqa serves f16 caches");
+    constexpr int hd = VEC * WAVE;
+    constexpr int KB = hd / 32;       // score MFMAs per 16 timesteps
+    constexpr int DB = hd / 16;       // 16-row blocks of O^T
+    constexpr int DCH = hd / 8;       // 16-byte chunks per cache row of the head
+    constexpr int NJ = DCH / 2;       // timesteps a lane stages of V: 8 or 4
+    constexpr int NG = NJ / 4;        // groups of 4 consecutive timesteps in them
+    using VCol = _Float16 __attribute__((ext_vector_type(NJ)));
+    // the V^T tiles of the waves; after the loop, the waves' O partials
+    __shared__ __attribute__((aligned(16))) char smem[GQA_NW * hd * GQA_VLD * 2];
+    __shared__ float sm[GQA_NW][GQA_HEADS], sl[GQA_NW][GQA_HEADS];
+    static_assert(sizeof(smem) >= GQA_NW * GQA_HEADS * hd * sizeof(float),
+                  "the O partials fit the V tiles");
+
+    const int kvh = blockIdx.x;
+    const int b = blockIdx.y;
+    const int sp = blockIdx.z;
+    const int S = gridDim.z;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+    const int lane = threadIdx.x % WAVE;
+    const int n = lane & 15;  // query head of the KV head; K row of a fragment
+    const int g = lane >> 4;  // k group
+    // V staging: k group, chunk of the row, and which NJ of the group's 8
+    const int vg = lane & 3;
+    const int vdc = (lane >> 2) % DCH;
+    const int vj0 = (lane >> 2) / DCH * NJ;
+
+    const int pos = rows.position(b);
+    const int last = pos >> 5;  // the tile that holds the position
+    const _Float16 *kc = reinterpret_cast<const _Float16 *>(kc_all)
+                       + rows.cache_base(b) * kv_dim0 + kvh * hd;
+    const _Float16 *vc = reinterpret_cast<const _Float16 *>(vc_all)
+                       + rows.cache_base(b) * kv_dim0 + kvh * hd;
+    _Float16 *sv = reinterpret_cast<_Float16 *>(smem) + wave * hd * GQA_VLD;
+
+    // Paged: a K fragment row has its own page; a V group of 4 consecutive
+    // timesteps starts at a multiple of 4 and lies in one page (P >= 4).
+    // With pages of 32 rows or more the tile lies in one page: one uniform
+    // id. A timestep past pos looks up the page of pos.
+    struct Ids { int k[2], v[NG]; };
+    struct Tile { v8h_t k[2][KB], v[NJ]; };
+    [[maybe_unused]] const int *seqp = nullptr;
+    [[maybe_unused]] int pshift = 0;
+    if constexpr (ROWS::kPaged) {
+        seqp = rows.seq_pages(b);
+        pshift = rows.shift;
+    }
+    // tile-local timestep of k index j of this lane's V group
+    auto vt = [&](int j) { return 16 * (j >> 2) + 4 * vg + (j & 3); };
+    auto fetch_ids = [&](int tile) {
+        Ids id{};
+        if constexpr (ROWS::kPaged) {
+            const int t0 = tile * GQA_T;
+            if (pshift >= 5) {
+                const int x = seqp[min(t0, pos) >> pshift];
+                id.k[0] = id.k[1] = x;
+                #pragma unroll
+                for (int c = 0; c < NG; c++) id.v[c] = x;
+            } else {
+                #pragma unroll
+                for (int u = 0; u < 2; u++)
+                    id.k[u] = seqp[min(t0 + 16 * u + n, pos) >> pshift];
+                #pragma unroll
+                for (int c = 0; c < NG; c++)
+                    id.v[c] = seqp[min(t0 + vt(vj0 + 4 * c), pos) >> pshift];
+            }
+        }
+        return id;
+    };
+    // cache row (relative to kc / vc) of timestep t <= pos
+    auto row_of = [&](int t, int id) {
+        if constexpr (ROWS::kPaged)
+            return ((int64_t)id << pshift) + (t & ((1 << pshift) - 1));
+        else
+            return (int64_t)t;
+    };
+    auto load = [&](int tile, const Ids &id, Tile &x) {
+        const int t0 = tile * GQA_T;
+        #pragma unroll
+        for (int u = 0; u < 2; u++) {
+            const int t = min(t0 + 16 * u + n, pos);
+            const _Float16 *p = kc + row_of(t, id.k[u]) * kv_dim0 + 8 * g;
+            #pragma unroll
+            for (int kb = 0; kb < KB; kb++)
+                x.k[u][kb] = *reinterpret_cast<const v8h_t *>(p + 32 * kb);
+        }
+        #pragma unroll
+        for (int jj = 0; jj < NJ; jj++) {
+            const int t = min(t0 + vt(vj0 + jj), pos);
+            x.v[jj] = *reinterpret_cast<const v8h_t *>(
+                vc + row_of(t, id.v[jj >> 2]) * kv_dim0 + 8 * vdc);
+        }
+    };
+
+    // q * scale in f32, rounded to f16 once: the B operand of the scores.
+    // Heads at or past kv_mul are padding, never stored: they load the last
+    // head (no guarded load, no wait per load) and scale it by 0.
+    const float qs = n < kv_mul ? scale : 0.0f;
+    const float *qp = q + (int64_t)b * q_ld
+                    + (kvh * kv_mul + min(n, kv_mul - 1)) * hd + 8 * g;
+    v8h_t qf[KB];
+    #pragma unroll
+    for (int kb = 0; kb < KB; kb++) {
+        const float4 x0 = *reinterpret_cast<const float4 *>(qp + 32 * kb);
+        const float4 x1 = *reinterpret_cast<const float4 *>(qp + 32 * kb + 4);
+        qf[kb] = v8h_t{
+            (_Float16)mul_f32(x0.x, qs), (_Float16)mul_f32(x0.y, qs),
+            (_Float16)mul_f32(x0.z, qs), (_Float16)mul_f32(x0.w, qs),
+            (_Float16)mul_f32(x1.x, qs), (_Float16)mul_f32(x1.y, qs),
+            (_Float16)mul_f32(x1.z, qs), (_Float16)mul_f32(x1.w, qs)};
+    }
+
+    v4f_t o[DB];
+    #pragma unroll
+    for (int db = 0; db < DB; db++) o[db] = v4f_t{0.f, 0.f, 0.f, 0.f};
+    // m is the head's, equal in the four lanes that hold it; l is this
+    // lane's quarter (its 8 timesteps per tile), summed at the end
+    float m = -1e30f, l = 0.0f;
+
+    auto compute = [&](int tile, const Tile &x) {
+        // V^T into the wave's tile: row d = the 32 timesteps in k order
+        #pragma unroll
+        for (int i = 0; i < 8; i++) {
+            VCol col;
+            #pragma unroll
+            for (int jj = 0; jj < NJ; jj++) col[jj] = x.v[jj][i];
+            *reinterpret_cast<VCol *>(
+                &sv[(8 * vdc + i) * GQA_VLD + 8 * vg + vj0]) = col;
+        }
+        // the fragment reads below are other lanes' stores: keep the order
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        v4f_t s[2];
+        #pragma unroll
+        for (int u = 0; u < 2; u++) {
+            s[u] = v4f_t{0.f, 0.f, 0.f, 0.f};
+            #pragma unroll
+            for (int kb = 0; kb < KB; kb++)
+                s[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                    x.k[u][kb], qf[kb], s[u], 0, 0, 0);
+        }
+        // only the tile that holds the position masks
+        const bool edge = tile == last;
+        const int tl = tile * GQA_T + 4 * g;  // timestep of s[0][0]
+        float mx = -1e30f;
+        #pragma unroll
+        for (int u = 0; u < 2; u++)
+            #pragma unroll
+            for (int r = 0; r < 4; r++) {
+                if (edge && tl + 16 * u + r > pos) s[u][r] = -1e30f;
+                mx = fmaxf(mx, s[u][r]);
+            }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, WAVE));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, WAVE));
+        // the tile's first timestep is at or below pos: mx is a real score
+        const float mn = fmaxf(m, mx);
+        constexpr float LOG2E = 1.4426950408889634f;
+        const float nmn = -mn * LOG2E;
+        // m = -1e30 (the wave's first tile): l and o are 0, any finite f does
+        const float f = m > -1e30f
+            ? __builtin_amdgcn_exp2f(fma_f32(m, LOG2E, nmn)) : 0.0f;
+        v8h_t pf;
+        float ls = 0.0f;
+        #pragma unroll
+        for (int u = 0; u < 2; u++)
+            #pragma unroll
+            for (int r = 0; r < 4; r++) {
+                // a masked weight is 0 by name, not left to exp: its bits
+                // are cleared (a select would put a branch around each exp)
+                const unsigned keep =
+                    (edge && tl + 16 * u + r > pos) ? 0u : ~0u;
+                const float p = __uint_as_float(keep & __float_as_uint(
+                    __builtin_amdgcn_exp2f(fma_f32(s[u][r], LOG2E, nmn))));
+                ls += p;
+                pf[4 * u + r] = (_Float16)p;
+            }
+        l = fma_f32(l, f, ls);
+        m = mn;
+        #pragma unroll
+        for (int db = 0; db < DB; db++) {
+            #pragma unroll
+            for (int r = 0; r < 4; r++) o[db][r] = mul_f32(o[db][r], f);
+            const v8h_t vf = *reinterpret_cast<const v8h_t *>(
+                &sv[(16 * db + n) * GQA_VLD + 8 * g]);
+            o[db] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pf, o[db],
+                                                           0, 0, 0);
+        }
+        // the next tile's stores come behind these reads
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    };
+
+    // a wave with no tile keeps m = -1e30, l = 0, o = 0
+    const int step = GQA_NW * S;
+    int tile = sp + S * wave;
+    if (tile <= last) {
+        Tile ta, tb;
+        Ids id = fetch_ids(tile);
+        load(tile, id, ta);
+        id = fetch_ids(tile + step);
+        for (;;) {
+            // ids first: waiting for them later must not drain the K/V loads
+            Ids nid = fetch_ids(tile + 2 * step);
+            load(tile + step, id, tb);
+            id = nid;
+            compute(tile, ta);
+            tile += step;
+            if (tile > last) break;
+            nid = fetch_ids(tile + 2 * step);
+            load(tile + step, id, ta);
+            id = nid;
+            compute(tile, tb);
+            tile += step;
+            if (tile > last) break;
+        }
+    }
+
+    // merge the four waves in wave order, as k_attn_split does
+    l += __shfl_xor(l, 16, WAVE);
+    l += __shfl_xor(l, 32, WAVE);
+    __syncthreads();  // every wave is done with its V tile
+    float *so = reinterpret_cast<float *>(smem);  // [wave][head][hd]
+    if (n < kv_mul) {
+        if (g == 0) { sm[wave][n] = m; sl[wave][n] = l; }
+        #pragma unroll
+        for (int db = 0; db < DB; db++)
+            *reinterpret_cast<v4f_t *>(
+                &so[(wave * GQA_HEADS + n) * hd + 16 * db + 4 * g]) = o[db];
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < kv_mul * hd; e += GQA_NW * WAVE) {
+        const int hn = e / hd, d = e % hd;
+        float M = -1e30f;
+        #pragma unroll
+        for (int w = 0; w < GQA_NW; w++) M = fmaxf(M, sm[w][hn]);
+        // all four empty: M = -1e30, every weight 1, l = 0 and o = 0
+        float L = 0.0f, acc = 0.0f;
+        #pragma unroll
+        for (int w = 0; w < GQA_NW; w++) {
+            const float fw = __expf(sm[w][hn] - M);
+            L = fmaf(sl[w][hn], fw, L);
+            acc = fmaf(so[(w * GQA_HEADS + hn) * hd + d], fw, acc);
+        }
+        const int64_t slot =
+            ((int64_t)b * n_heads0 + kvh * kv_mul + hn) * S + sp;
+        o_scratch[slot * hd + d] = acc;
+        if (d == 0) {
+            ml_scratch[slot * 2] = M;
+            ml_scratch[slot * 2 + 1] = L;
+        }
+    }
+}
+
 // ------------------------------------------------------------------ rope
 // style 0 = llama interleaved pairs (reference ropeLlama_F32,
 // nn-cpu-ops.cpp:843-863), style 1 = falcon/neox half-rotated
@@ -1789,6 +2096,108 @@ void attn_chunk_paged(torch::Tensor q, int64_t q_ld, torch::Tensor kc,
                       ml_scratch, o_scratch, zq, zs, zbs, k_scales, v_scales);
 }
 
+// Decode-row attention with the query heads of a KV head packed into the
+// MFMA: k_attn_gqa fills the split scratch (any splits >= 1), the combine
+// finishes. f16 caches only: `other` names the binding that serves the rest.
+template <typename ROWS>
+static void attn_gqa_launch(const char *name, const char *other,
+                            torch::Tensor &q, int64_t q_ld, torch::Tensor &kc,
+                            torch::Tensor &vc, torch::Tensor &y, ROWS rows,
+                            int64_t batch, int64_t n_heads0, int64_t kv_mul,
+                            int64_t head_dim, int64_t splits,
+                            torch::Tensor &ml_scratch, torch::Tensor &o_scratch,
+                            OptTensor &zq, OptTensor &zs, OptTensor &zbs,
+                            const OptTensor &k_scales,
+                            const OptTensor &v_scales) {
+    CHECK_CUDA(q);
+    TORCH_CHECK(kc.scalar_type() == at::kHalf && vc.scalar_type() == at::kHalf,
+                name, " serves a float16 KV cache: use ", other,
+                " for a float32 or an int8 (Q80) cache");
+    TORCH_CHECK(!k_scales.has_value() && !v_scales.has_value(), name,
+                " takes no k_scales / v_scales: use ", other,
+                " for an int8 (Q80) cache");
+    TORCH_CHECK(head_dim == 64 || head_dim == 128, name,
+                " serves head_dim 64 and 128 (got ", head_dim, "): use ", other);
+    TORCH_CHECK(kv_mul >= 1 && kv_mul <= GQA_HEADS, name, " serves kv_mul 1..",
+                GQA_HEADS, " (got ", kv_mul, "): use ", other);
+    TORCH_CHECK(n_heads0 % kv_mul == 0, name, ": n_heads0 (", n_heads0,
+                ") must be a multiple of kv_mul (", kv_mul, ")");
+    TORCH_CHECK(batch >= 1 && splits >= 1 && q_ld % 4 == 0 && kc.dim() == 2
+                && kc.is_contiguous() && vc.is_contiguous()
+                && kc.sizes() == vc.sizes()
+                && kc.size(1) == n_heads0 / kv_mul * head_dim,
+                name, ": contiguous caches [rows, n_kv_heads0 * head_dim], "
+                "q_ld a multiple of 4");
+    const int64_t slots = batch * n_heads0 * splits;
+    TORCH_CHECK(ml_scratch.numel() >= slots * 2
+                && o_scratch.numel() >= slots * head_dim,
+                name, ": split scratch too small for ", slots, " partials");
+    const bool quant = zq.has_value();
+    float *yp = quant ? nullptr : y.data_ptr<float>();
+    int8_t *zqp = quant ? zq->data_ptr<int8_t>() : nullptr;
+    float *zsp = quant ? zs->data_ptr<float>() : nullptr;
+    float *zbsp = quant ? zbs->data_ptr<float>() : nullptr;
+    const __half *kcp = reinterpret_cast<__half *>(kc.data_ptr<at::Half>());
+    const __half *vcp = reinterpret_cast<__half *>(vc.data_ptr<at::Half>());
+    with_head_vec(head_dim, [&](auto vec_const) {
+        constexpr int V = decltype(vec_const)::value;
+        hipLaunchKernelGGL((k_attn_gqa<V, __half, ROWS>),
+                           dim3(n_heads0 / kv_mul, batch, splits),
+                           dim3(GQA_NW * WAVE), 0, cur_stream(),
+                           q.data_ptr<float>(), (int)q_ld, kcp, vcp, rows,
+                           (int)n_heads0, (int)kv_mul, (int)kc.size(1),
+                           1.0f / sqrtf((float)head_dim),
+                           ml_scratch.data_ptr<float>(),
+                           o_scratch.data_ptr<float>());
+        combine_launch<V>(ml_scratch, o_scratch, yp, zqp, zsp, zbsp, batch,
+                          n_heads0, splits);
+    });
+}
+
+// attn for decode rows of one sequence: row b is position pos[0]+b.
+void attn_gqa(torch::Tensor q, int64_t q_ld, torch::Tensor kc, torch::Tensor vc,
+              torch::Tensor y, torch::Tensor pos, int64_t batch,
+              int64_t n_heads0, int64_t kv_mul, int64_t head_dim,
+              int64_t splits, torch::Tensor ml_scratch, torch::Tensor o_scratch,
+              OptTensor zq = c10::nullopt, OptTensor zs = c10::nullopt,
+              OptTensor zbs = c10::nullopt, OptTensor k_scales = c10::nullopt,
+              OptTensor v_scales = c10::nullopt) {
+    attn_gqa_launch("attn_gqa", "attn", q, q_ld, kc, vc, y,
+                    SeqRows{pos.data_ptr<int>()}, batch, n_heads0, kv_mul,
+                    head_dim, splits, ml_scratch, o_scratch, zq, zs, zbs,
+                    k_scales, v_scales);
+}
+
+void attn_gqa_rows(torch::Tensor q, int64_t q_ld, torch::Tensor kc,
+                   torch::Tensor vc, torch::Tensor y, torch::Tensor rows,
+                   int64_t batch, int64_t n_heads0, int64_t kv_mul,
+                   int64_t head_dim, int64_t splits, torch::Tensor ml_scratch,
+                   torch::Tensor o_scratch, OptTensor zq = c10::nullopt,
+                   OptTensor zs = c10::nullopt, OptTensor zbs = c10::nullopt,
+                   OptTensor k_scales = c10::nullopt,
+                   OptTensor v_scales = c10::nullopt) {
+    attn_gqa_launch("attn_gqa_rows", "attn_rows", q, q_ld, kc, vc, y,
+                    table_rows(rows, batch), batch, n_heads0, kv_mul, head_dim,
+                    splits, ml_scratch, o_scratch, zq, zs, zbs, k_scales,
+                    v_scales);
+}
+
+void attn_gqa_paged(torch::Tensor q, int64_t q_ld, torch::Tensor kc,
+                    torch::Tensor vc, torch::Tensor y, torch::Tensor rows,
+                    torch::Tensor page_table, int64_t page_size, int64_t batch,
+                    int64_t n_heads0, int64_t kv_mul, int64_t head_dim,
+                    int64_t splits, torch::Tensor ml_scratch,
+                    torch::Tensor o_scratch, OptTensor zq = c10::nullopt,
+                    OptTensor zs = c10::nullopt, OptTensor zbs = c10::nullopt,
+                    OptTensor k_scales = c10::nullopt,
+                    OptTensor v_scales = c10::nullopt) {
+    TORCH_CHECK(kc.dim() == 2, "attn_gqa_paged: caches are [rows, kv_dim0]");
+    attn_gqa_launch("attn_gqa_paged", "attn_paged", q, q_ld, kc, vc, y,
+                    paged_rows(rows, page_table, page_size, batch, kc), batch,
+                    n_heads0, kv_mul, head_dim, splits, ml_scratch, o_scratch,
+                    zq, zs, zbs, k_scales, v_scales);
+}
+
 // The Q80 write kernel for either launcher below; mode as k_rope_kv_q80's
 // MODE (0/1 = the rope style, 2 = q/k-norm + neox).
 template <typename ROWS>
@@ -2014,6 +2423,26 @@ void register_attn(py::module &m) {
           py::arg("n_runs"), py::arg("batch"), py::arg("n_heads0"),
           py::arg("kv_mul"), py::arg("head_dim"), py::arg("splits"),
           py::arg("ml_scratch"), py::arg("o_scratch"),
+          py::arg("zq") = py::none(), py::arg("zs") = py::none(),
+          py::arg("zbs") = py::none(), KV_SCALE_ARGS);
+    m.def("attn_gqa", &attn_gqa, py::arg("q"), py::arg("q_ld"), py::arg("kc"),
+          py::arg("vc"), py::arg("y"), py::arg("pos"), py::arg("batch"),
+          py::arg("n_heads0"), py::arg("kv_mul"), py::arg("head_dim"),
+          py::arg("splits"), py::arg("ml_scratch"), py::arg("o_scratch"),
+          py::arg("zq") = py::none(), py::arg("zs") = py::none(),
+          py::arg("zbs") = py::none(), KV_SCALE_ARGS);
+    m.def("attn_gqa_rows", &attn_gqa_rows, py::arg("q"), py::arg("q_ld"),
+          py::arg("kc"), py::arg("vc"), py::arg("y"), py::arg("rows"),
+          py::arg("batch"), py::arg("n_heads0"), py::arg("kv_mul"),
+          py::arg("head_dim"), py::arg("splits"), py::arg("ml_scratch"),
+          py::arg("o_scratch"), py::arg("zq") = py::none(),
+          py::arg("zs") = py::none(), py::arg("zbs") = py::none(),
+          KV_SCALE_ARGS);
+    m.def("attn_gqa_paged", &attn_gqa_paged, py::arg("q"), py::arg("q_ld"),
+          py::arg("kc"), py::arg("vc"), py::arg("y"), py::arg("rows"),
+          py::arg("page_table"), py::arg("page_size"), py::arg("batch"),
+          py::arg("n_heads0"), py::arg("kv_mul"), py::arg("head_dim"),
+          py::arg("splits"), py::arg("ml_scratch"), py::arg("o_scratch"),
           py::arg("zq") = py::none(), py::arg("zs") = py::none(),
           py::arg("zbs") = py::none(), KV_SCALE_ARGS);
     m.def("kv_append", &kv_append);

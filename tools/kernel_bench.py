@@ -105,6 +105,59 @@ def chunk_ab(positions=(512, 2048, 4096, 8192), batches=(32,), rounds=3,
                   + f"  max |dcode| {diff}")
 
 
+def gqa_ab(positions=(512, 2048, 4096, 8192), batches=(1, 8, 32), rounds=5,
+           gqa_splits=(4, 8, 16, 32)):
+    """Decode-row attention alone in an isolated hipGraph at the 8B shape (32
+    heads, kv_mul 4, hd 128, f16 KV, Q80 output): B rows of B distinct
+    sequences, all at position p. k_attn_split + combine (attn_rows) at the
+    decode schedule's S against k_attn_gqa + combine (attn_gqa_rows) at the
+    same S and at every S of gqa_splits, interleaved over `rounds`: median
+    (min..max) us per call, the fraction of 6.3 TB/s that the distinct K/V
+    bytes reach at the schedule's S, and the largest |code| difference
+    between the two Q80 outputs there.
+
+      python tools/kernel_bench.py gqa"""
+    H0, hd, kvd, kv_mul = 32, 128, 1024, 4
+    seq = max(positions) + 64
+    print("\n-- decode-row attention, isolated graph, 8B shape, f16 KV, Q80 out "
+          "(us per call: median (min..max)) --")
+    for B in batches:
+        kc = (torch.randn(B * seq, kvd, device=dev, generator=g) * 0.3).half()
+        vc = torch.randn(B * seq, kvd, device=dev, generator=g).half()
+        qv = torch.randn(B, H0 * hd, device=dev, generator=g)
+        y = torch.zeros(B, H0 * hd, device=dev)
+        z = [[torch.zeros(B, H0 * hd, dtype=torch.int8, device=dev),
+              torch.zeros(B, H0 * hd // 32, device=dev),
+              torch.zeros(B, H0 * hd // 32, device=dev)] for _ in range(2)]
+        for p in positions:
+            rows = torch.tensor([[b * seq, p] for b in range(B)],
+                                dtype=torch.int32, device=dev)
+            S0 = 8 if p < 512 else 16 if p < 2048 else 32
+            cands = {}
+            for name, S in [("split", S0), ("gqa", S0)] + [
+                    (f"gqa S={S}", S) for S in gqa_splits if S != S0]:
+                ml = torch.zeros(B * H0 * S * 2, device=dev)
+                osc = torch.zeros(B * H0 * S * hd, device=dev)
+                fn = k.attn_rows if name == "split" else k.attn_gqa_rows
+                cands[name] = (lambda fn=fn, S=S, ml=ml, osc=osc, zz=z[
+                    name != "split"]: fn(qv, H0 * hd, kc, vc, y, rows, B, H0,
+                                         kv_mul, hd, S, ml, osc, *zz))
+            t = {name: [] for name in cands}
+            for _ in range(rounds):
+                for name, fn in cands.items():
+                    t[name].append(bench(fn, n=16, reps=3))
+            cands["split"](), cands["gqa"]()
+            diff = (z[0][0].int() - z[1][0].int()).abs().max().item()
+            nbytes = B * (p + 1) * kvd * 2 * 2  # distinct K and V bytes
+            tbs = nbytes / statistics.median(t["gqa"]) / 1e6
+            print(f"B={B:2d} pos={p:5d} S={S0:2d}  " + "  ".join(
+                f"{name}: {statistics.median(v):6.1f} ({min(v):.1f}..{max(v):.1f})"
+                for name, v in t.items())
+                + f"  gqa {tbs:4.2f} TB/s ({100 * tbs / 6.3:2.0f}% of 6.3)"
+                f"  max |dcode| {diff}")
+        del kc, vc
+
+
 def chunk_forms_ab(kv_dtype="f16", page_size=0, positions=(512, 2048, 4096, 8192),
                    batches=(32,), rounds=3):
     """The paged and Q80 forms of the chunk attention in an isolated hipGraph
@@ -345,6 +398,9 @@ if sys.argv[1:2] in (["chunk"], ["chunk-rows"]) and len(sys.argv) > 2:
     sys.exit(0)
 if sys.argv[1:] == ["chunk"]:
     chunk_ab()
+    sys.exit(0)
+if sys.argv[1:] == ["gqa"]:
+    gqa_ab()
     sys.exit(0)
 if sys.argv[1:] == ["chunk-rows"]:
     chunk_ab(positions=(512, 4096), batches=(4, 8, 16, 32), splits=(16, 32))
