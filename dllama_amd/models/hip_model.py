@@ -288,9 +288,12 @@ class HipTransformer:
         # decode rows on the matrix cores: steps above the wide tier that the
         # chunk kernel does not take run k_attn_gqa (the kv_mul query heads
         # of a KV head are the MFMA N dimension, K/V read once per KV head
-        # and row) instead of k_attn_split, for an f16 cache. Off by default
-        # (docs/DESIGN.md §13); set_gqa_attn on a live model
-        self.gqa_attn = flag("DLLAMA_ATTN_GQA", "0")
+        # and row) instead of k_attn_split. Level 1 serves f16 caches; level 2
+        # (gqa_attn_q80) Q80 caches as well, whose K and V enter the MFMA as
+        # f16(code * scale). Off by default (docs/DESIGN.md §13);
+        # set_gqa_attn on a live model
+        self.gqa_attn = env.get("DLLAMA_ATTN_GQA", "0") in ("1", "2")
+        self.gqa_attn_q80 = env.get("DLLAMA_ATTN_GQA", "0") == "2"
         # a single-sequence decode step below this position keeps the split
         # pair: one row at S=16 is too little work for the MFMA kernel (12.3
         # against 9.9 us at position 512, 18.3 against 23.7 at 2048, the
@@ -299,7 +302,13 @@ class HipTransformer:
         # at every position above the wide tier: from 8 rows it won wherever
         # it was measured (profiles/r17_gqa_decode_attention.md)
         self.gqa_min_pos = 2048
+        # a Q80 cache has its own crossover: k_attn_split is faster on it
+        # (15.7 against 23.7 us at position 2048) and wins or ties up to
+        # 3072 (18.5 against 18.7); 3584 is the first measured position where
+        # the MFMA kernel wins, 19.0 against 28.9 (profiles/r18_gqa_q80.md)
+        self.gqa_min_pos_q80 = 3584
         self._gqa_pos_ok = True  # the last _pick_splits: at or above it
+        self._gqa_seq_ok = True  # the same of the last single-sequence step
         # the S in force above the wide tier, put back when a step leaves it
         self._splits_above = self.attn_splits if self.attn_splits != 1 else 8
         # measured-slower fusions kept for shape experiments (profiles r02):
@@ -662,7 +671,8 @@ class HipTransformer:
                 self.qkv_out, self.qkv_ld, self.k_cache[l], self.v_cache[l],
                 self.zbuf[:B], *addr.where, B, c.n_heads0, self.kv_mul,
                 c.head_dim, self.attn_splits, self.attn_ml, self.attn_o,
-                *(self.zq.triple() if emit_q80 else ()))
+                *(self.zq.triple() if emit_q80 else ()),
+                **self._kv_scales(l))
             return
         getattr(self.k, addr.attn)(
             self.qkv_out, self.qkv_ld, self.k_cache[l], self.v_cache[l],
@@ -673,18 +683,23 @@ class HipTransformer:
 
     def _gqa_step(self) -> bool:
         """A step the chunk kernel left takes the GQA-packed MFMA attention:
-        the option is on, the cache is f16, the kernel has an instantiation
-        for the heads, the step is above the wide tier (S > 1) and, for a
-        single sequence, at or above gqa_min_pos."""
-        return bool(self.gqa_attn and self.kv_dtype == "f16"
+        the option is on, the cache is f16 (or Q80 at the option's second
+        level), the kernel has an instantiation for the heads, the step is
+        above the wide tier (S > 1) and, for a single sequence, at or above
+        gqa_min_pos."""
+        served = self.kv_dtype == "f16" or (
+            self.kv_dtype == "q80" and self.gqa_attn_q80)
+        return bool(self.gqa_attn and served
                     and self.cfg.head_dim in (64, 128) and self.kv_mul <= 16
                     and self.attn_splits > 1 and self._gqa_pos_ok)
 
-    def set_gqa_attn(self, on: bool = True):
+    def set_gqa_attn(self, on: bool = True, q80: bool = False):
         """Decode rows above the wide tier take the GQA-packed MFMA attention
-        (or stop taking it). Drops the captured graphs: a step's graph holds
-        one kernel or the other."""
+        (or stop taking it); q80=True extends it to a Q80 KV cache, which
+        `on` alone leaves on its old launches. Drops the captured graphs: a
+        step's graph holds one kernel or the other."""
         self.gqa_attn = bool(on)
+        self.gqa_attn_q80 = bool(on) and bool(q80)
         self.graphs.clear()
 
     def _chunk_step(self, B: int, addr: KVAddr):
@@ -1562,7 +1577,15 @@ class HipTransformer:
         # and skips the wide tier; S=1 is never handed to the pair there.
         # set_wide_rows turns the tier on for row steps: BatchEngine calls
         # it.
-        self._gqa_pos_ok = rows or pos >= self.gqa_min_pos
+        q80 = self.kv_q80 and self.gqa_attn_q80
+        self._gqa_pos_ok = rows or pos >= (
+            self.gqa_min_pos_q80 if q80 else self.gqa_min_pos)
+        if not rows:
+            # gqa_min_pos_q80 is no S boundary: the decode graph captured
+            # below it holds the other kernel
+            if q80 and self._gqa_pos_ok != self._gqa_seq_ok:
+                self.graphs.clear()
+            self._gqa_seq_ok = self._gqa_pos_ok
         if not self.adaptive_thresh:
             return self.attn_splits
         if ((self.wide_rows or not rows)

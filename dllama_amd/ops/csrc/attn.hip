@@ -786,6 +786,22 @@ __device__ __forceinline__ v8h_t q80_codes_f16(int2 c, _Float16 d) {
     return out * d;
 }
 
+// The same values for the 4 codes of one dword, without a sign extension per
+// byte. code ^ 0x80 = code + 128 as an unsigned byte u; a half with the bits
+// 0x6400 | u is 1024 + u exactly (exponent 2^10, u in the low mantissa bits),
+// so two byte permutes build the four halves 1152 + code, one packed add of
+// -1152 leaves f16(code) (an integer below 2^11: exact), and the packed
+// multiply rounds code * d once as above.
+__device__ __forceinline__ v4h_t q80_dword_f16(int w, _Float16 d) {
+    const unsigned u = (unsigned)w ^ 0x80808080u;
+    // selector bytes 0..3 take bytes of the second operand, 4 a byte 0x64
+    const unsigned lo = __builtin_amdgcn_perm(0x64646464u, u, 0x04010400u);
+    const unsigned hi = __builtin_amdgcn_perm(0x64646464u, u, 0x04030402u);
+    typedef unsigned v2u_t __attribute__((ext_vector_type(2)));
+    const v4h_t biased = __builtin_bit_cast(v4h_t, v2u_t{lo, hi});
+    return (biased - (_Float16)1152.0f) * d;
+}
+
 template <int VEC, typename KVT, typename ROWS>
 __global__ void __launch_bounds__(CHUNK_NW * WAVE, 2)
 k_attn_chunk(const float *__restrict__ q, int q_ld,
@@ -1104,6 +1120,19 @@ k_attn_chunk(const float *__restrict__ q, int q_ld,
 //
 // Rounding points are k_attn_chunk's: q*scale (f32) -> f16 once, P -> f16
 // per tile; scores, m, l and O accumulate in f32.
+//
+// Q80 form (KVT = int8_t, ROWS = Q80Rows<..>): the same kernel but for how a
+// tile becomes MFMA operands, K and V entering as f16(code * scale)
+// (q80_dword_f16). K: lane g of the four that hold a K row takes one
+// contiguous quarter of it, hd/4 codes = one block or half of one, so one
+// scale; fragment kb is its codes 8 kb .. 8 kb + 7, converted in registers
+// before the MFMA, and q is permuted the same way. V: a row of the head is 8
+// pieces of hd/8 codes; lane (vg, u, dc) = (lane & 3, (lane >> 2) & 1,
+// lane >> 3) loads piece dc of the 4 consecutive rows 16 u + 4 vg + 0..3 and
+// their scales (a load instruction reads 8 whole rows of the head; the 4
+// rows lie in one page), converts, transposes in registers and stores 4
+// halves per d into the same V^T tile. A tile set is 38 registers against 64
+// at head_dim 128: the ring stays two sets and a third wave fits the SIMD.
 typedef float v4f_t __attribute__((ext_vector_type(4)));
 
 constexpr int GQA_T = 32;      // timesteps per tile = MFMA K of O^T += V^T P^T
@@ -1117,13 +1146,21 @@ k_attn_gqa(const float *__restrict__ q, int q_ld,
            const KVT *__restrict__ kc_all, const KVT *__restrict__ vc_all,
            const ROWS rows, int n_heads0, int kv_mul, int kv_dim0, float scale,
            float *__restrict__ ml_scratch, float *__restrict__ o_scratch) {
-    static_assert(std::is_same_v<KVT, __half>, "k_attn_gqa serves f16 caches");
+    constexpr bool Q8 = kKVQ80<KVT>;
+    static_assert(Q8 || std::is_same_v<KVT, __half>,
+                  "k_attn_gqa serves f16 and Q80 caches");
     constexpr int hd = VEC * WAVE;
     constexpr int KB = hd / 32;       // score MFMAs per 16 timesteps
     constexpr int DB = hd / 16;       // 16-row blocks of O^T
     constexpr int DCH = hd / 8;       // 16-byte chunks per cache row of the head
-    constexpr int NJ = DCH / 2;       // timesteps a lane stages of V: 8 or 4
+    constexpr int VP = Q8 ? 8 : DCH;  // pieces a V row of the head is staged in
+    constexpr int NJ = VP / 2;        // timesteps a lane stages of V: 8 or 4
     constexpr int NG = NJ / 4;        // groups of 4 consecutive timesteps in them
+    // Q80: dwords of codes a lane holds of a K row (a quarter of the head)
+    // and of a V row (one of VP pieces)
+    constexpr int KW = hd / 16, VW = hd / 32;
+    typedef int KCodes __attribute__((ext_vector_type(4)));
+    typedef int VCodes __attribute__((ext_vector_type(VW)));
     using VCol = _Float16 __attribute__((ext_vector_type(NJ)));
     // the V^T tiles of the waves; after the loop, the waves' O partials
     __shared__ __attribute__((aligned(16))) char smem[GQA_NW * hd * GQA_VLD * 2];
@@ -1140,16 +1177,27 @@ k_attn_gqa(const float *__restrict__ q, int q_ld,
     const int n = lane & 15;  // query head of the KV head; K row of a fragment
     const int g = lane >> 4;  // k group
     // V staging: k group, chunk of the row, and which NJ of the group's 8
+    // (Q80: both halves of a k group sit in one half-wave, so that a store
+    // instruction spreads over twice the LDS banks)
     const int vg = lane & 3;
-    const int vdc = (lane >> 2) % DCH;
-    const int vj0 = (lane >> 2) / DCH * NJ;
+    const int vdc = Q8 ? lane >> 3 : (lane >> 2) % DCH;
+    const int vj0 = Q8 ? lane & 4 : (lane >> 2) / DCH * NJ;
 
     const int pos = rows.position(b);
     const int last = pos >> 5;  // the tile that holds the position
-    const _Float16 *kc = reinterpret_cast<const _Float16 *>(kc_all)
-                       + rows.cache_base(b) * kv_dim0 + kvh * hd;
-    const _Float16 *vc = reinterpret_cast<const _Float16 *>(vc_all)
-                       + rows.cache_base(b) * kv_dim0 + kvh * hd;
+    using KVE = std::conditional_t<Q8, int8_t, _Float16>;
+    const KVE *kc = reinterpret_cast<const KVE *>(kc_all)
+                  + rows.cache_base(b) * kv_dim0 + kvh * hd;
+    const KVE *vc = reinterpret_cast<const KVE *>(vc_all)
+                  + rows.cache_base(b) * kv_dim0 + kvh * hd;
+    // Q80: the scale planes, f16 [rows, kv_dim0/32], from the same cache row
+    [[maybe_unused]] const int nblk = kv_dim0 / QB;
+    [[maybe_unused]] const _Float16 *ks = nullptr, *vs = nullptr;
+    if constexpr (Q8) {
+        const int64_t sb = rows.cache_base(b) * nblk + kvh * (hd / QB);
+        ks = reinterpret_cast<const _Float16 *>(rows.ks) + sb;
+        vs = reinterpret_cast<const _Float16 *>(rows.vs) + sb;
+    }
     _Float16 *sv = reinterpret_cast<_Float16 *>(smem) + wave * hd * GQA_VLD;
 
     // Paged: a K fragment row has its own page; a V group of 4 consecutive
@@ -1157,7 +1205,15 @@ k_attn_gqa(const float *__restrict__ q, int q_ld,
     // With pages of 32 rows or more the tile lies in one page: one uniform
     // id. A timestep past pos looks up the page of pos.
     struct Ids { int k[2], v[NG]; };
-    struct Tile { v8h_t k[2][KB], v[NJ]; };
+    struct TileH { v8h_t k[2][KB], v[NJ]; };
+    // Q80: a quarter of each K row and a piece of 4 V rows as codes, and one
+    // scale per row
+    struct TileQ {
+        KCodes k[2][KW / 4];
+        VCodes v[NJ];
+        _Float16 ks[2], vs[NJ];
+    };
+    using Tile = std::conditional_t<Q8, TileQ, TileH>;
     [[maybe_unused]] const int *seqp = nullptr;
     [[maybe_unused]] int pshift = 0;
     if constexpr (ROWS::kPaged) {
@@ -1195,33 +1251,63 @@ k_attn_gqa(const float *__restrict__ q, int q_ld,
     };
     auto load = [&](int tile, const Ids &id, Tile &x) {
         const int t0 = tile * GQA_T;
-        #pragma unroll
-        for (int u = 0; u < 2; u++) {
-            const int t = min(t0 + 16 * u + n, pos);
-            const _Float16 *p = kc + row_of(t, id.k[u]) * kv_dim0 + 8 * g;
+        if constexpr (Q8) {
+            // K: the quarter g of the row (block g, or half of block g >> 1)
+            // and its one scale; V: piece vdc of 4 consecutive rows, a scale
+            // each. Both scales are read from the row the codes come from.
             #pragma unroll
-            for (int kb = 0; kb < KB; kb++)
-                x.k[u][kb] = *reinterpret_cast<const v8h_t *>(p + 32 * kb);
-        }
-        #pragma unroll
-        for (int jj = 0; jj < NJ; jj++) {
-            const int t = min(t0 + vt(vj0 + jj), pos);
-            x.v[jj] = *reinterpret_cast<const v8h_t *>(
-                vc + row_of(t, id.v[jj >> 2]) * kv_dim0 + 8 * vdc);
+            for (int u = 0; u < 2; u++) {
+                const int t = min(t0 + 16 * u + n, pos);
+                const int64_t r = row_of(t, id.k[u]);
+                const int8_t *p = kc + r * kv_dim0 + 4 * KW * g;
+                #pragma unroll
+                for (int w = 0; w < KW / 4; w++)
+                    x.k[u][w] = *reinterpret_cast<const KCodes *>(p + 16 * w);
+                x.ks[u] = ks[r * nblk + 4 * KW * g / QB];
+            }
+            #pragma unroll
+            for (int jj = 0; jj < NJ; jj++) {
+                const int t = min(t0 + vt(vj0 + jj), pos);
+                const int64_t r = row_of(t, id.v[0]);
+                x.v[jj] = *reinterpret_cast<const VCodes *>(
+                    vc + r * kv_dim0 + 4 * VW * vdc);
+                x.vs[jj] = vs[r * nblk + 4 * VW * vdc / QB];
+            }
+        } else {
+            #pragma unroll
+            for (int u = 0; u < 2; u++) {
+                const int t = min(t0 + 16 * u + n, pos);
+                const _Float16 *p =
+                    kc + row_of(t, id.k[u]) * kv_dim0 + 8 * g;
+                #pragma unroll
+                for (int kb = 0; kb < KB; kb++)
+                    x.k[u][kb] = *reinterpret_cast<const v8h_t *>(p + 32 * kb);
+            }
+            #pragma unroll
+            for (int jj = 0; jj < NJ; jj++) {
+                const int t = min(t0 + vt(vj0 + jj), pos);
+                x.v[jj] = *reinterpret_cast<const v8h_t *>(
+                    vc + row_of(t, id.v[jj >> 2]) * kv_dim0 + 8 * vdc);
+            }
         }
     };
 
     // q * scale in f32, rounded to f16 once: the B operand of the scores.
     // Heads at or past kv_mul are padding, never stored: they load the last
     // head (no guarded load, no wait per load) and scale it by 0.
+    // The MFMA only sums over k, so which d a lane's half j of fragment kb is
+    // is free as long as K and q agree: d = 32 kb + 8 g + j for an f16
+    // cache, d = (hd/4) g + 8 kb + j for a Q80 one, where lane g holds one
+    // contiguous quarter of the K row (one block, or half of one).
+    constexpr int QG = Q8 ? hd / 4 : 8, QKB = Q8 ? 8 : 32;
     const float qs = n < kv_mul ? scale : 0.0f;
     const float *qp = q + (int64_t)b * q_ld
-                    + (kvh * kv_mul + min(n, kv_mul - 1)) * hd + 8 * g;
+                    + (kvh * kv_mul + min(n, kv_mul - 1)) * hd + QG * g;
     v8h_t qf[KB];
     #pragma unroll
     for (int kb = 0; kb < KB; kb++) {
-        const float4 x0 = *reinterpret_cast<const float4 *>(qp + 32 * kb);
-        const float4 x1 = *reinterpret_cast<const float4 *>(qp + 32 * kb + 4);
+        const float4 x0 = *reinterpret_cast<const float4 *>(qp + QKB * kb);
+        const float4 x1 = *reinterpret_cast<const float4 *>(qp + QKB * kb + 4);
         qf[kb] = v8h_t{
             (_Float16)mul_f32(x0.x, qs), (_Float16)mul_f32(x0.y, qs),
             (_Float16)mul_f32(x0.z, qs), (_Float16)mul_f32(x0.w, qs),
@@ -1238,13 +1324,34 @@ k_attn_gqa(const float *__restrict__ q, int q_ld,
 
     auto compute = [&](int tile, const Tile &x) {
         // V^T into the wave's tile: row d = the 32 timesteps in k order
-        #pragma unroll
-        for (int i = 0; i < 8; i++) {
-            VCol col;
+        if constexpr (Q8) {
+            // the lane's piece of 4 consecutive rows, each times its scale,
+            // transposed in registers: 4 halves (8 bytes) per d
             #pragma unroll
-            for (int jj = 0; jj < NJ; jj++) col[jj] = x.v[jj][i];
-            *reinterpret_cast<VCol *>(
-                &sv[(8 * vdc + i) * GQA_VLD + 8 * vg + vj0]) = col;
+            for (int w = 0; w < VW; w++) {
+                v4h_t h[NJ];
+                #pragma unroll
+                for (int jj = 0; jj < NJ; jj++)
+                    h[jj] = q80_dword_f16(x.v[jj][w], x.vs[jj]);
+                #pragma unroll
+                for (int c = 0; c < 4; c++) {
+                    VCol col;
+                    #pragma unroll
+                    for (int jj = 0; jj < NJ; jj++) col[jj] = h[jj][c];
+                    *reinterpret_cast<VCol *>(
+                        &sv[(4 * VW * vdc + 4 * w + c) * GQA_VLD + 8 * vg
+                            + vj0]) = col;
+                }
+            }
+        } else {
+            #pragma unroll
+            for (int i = 0; i < 8; i++) {
+                VCol col;
+                #pragma unroll
+                for (int jj = 0; jj < NJ; jj++) col[jj] = x.v[jj][i];
+                *reinterpret_cast<VCol *>(
+                    &sv[(8 * vdc + i) * GQA_VLD + 8 * vg + vj0]) = col;
+            }
         }
         // the fragment reads below are other lanes' stores: keep the order
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -1253,9 +1360,22 @@ k_attn_gqa(const float *__restrict__ q, int q_ld,
         for (int u = 0; u < 2; u++) {
             s[u] = v4f_t{0.f, 0.f, 0.f, 0.f};
             #pragma unroll
-            for (int kb = 0; kb < KB; kb++)
+            for (int kb = 0; kb < KB; kb++) {
+                v8h_t kf;
+                if constexpr (Q8) {
+                    // codes 8 kb .. 8 kb + 7 of the lane's quarter
+                    const int w = 2 * kb;
+                    const v4h_t lo = q80_dword_f16(x.k[u][w / 4][w % 4],
+                                                   x.ks[u]);
+                    const v4h_t hi = q80_dword_f16(x.k[u][w / 4][w % 4 + 1],
+                                                   x.ks[u]);
+                    kf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                } else {
+                    kf = x.k[u][kb];
+                }
                 s[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                    x.k[u][kb], qf[kb], s[u], 0, 0, 0);
+                    kf, qf[kb], s[u], 0, 0, 0);
+            }
         }
         // only the tile that holds the position masks
         const bool edge = tile == last;
@@ -2098,7 +2218,8 @@ void attn_chunk_paged(torch::Tensor q, int64_t q_ld, torch::Tensor kc,
 
 // Decode-row attention with the query heads of a KV head packed into the
 // MFMA: k_attn_gqa fills the split scratch (any splits >= 1), the combine
-// finishes. f16 caches only: `other` names the binding that serves the rest.
+// finishes. f16 caches, and int8 (Q80) ones with their scale planes; `other`
+// names the binding that serves the rest.
 template <typename ROWS>
 static void attn_gqa_launch(const char *name, const char *other,
                             torch::Tensor &q, int64_t q_ld, torch::Tensor &kc,
@@ -2110,12 +2231,17 @@ static void attn_gqa_launch(const char *name, const char *other,
                             const OptTensor &k_scales,
                             const OptTensor &v_scales) {
     CHECK_CUDA(q);
-    TORCH_CHECK(kc.scalar_type() == at::kHalf && vc.scalar_type() == at::kHalf,
-                name, " serves a float16 KV cache: use ", other,
-                " for a float32 or an int8 (Q80) cache");
-    TORCH_CHECK(!k_scales.has_value() && !v_scales.has_value(), name,
-                " takes no k_scales / v_scales: use ", other,
-                " for an int8 (Q80) cache");
+    const bool f16 = kc.scalar_type() == at::kHalf
+                  && vc.scalar_type() == at::kHalf;
+    const bool q80 = kc.scalar_type() == at::kChar
+                  && vc.scalar_type() == at::kChar;
+    TORCH_CHECK(f16 || q80, name, " serves a float16 or an int8 (Q80) KV "
+                "cache: use ", other, " for a float32 cache");
+    TORCH_CHECK(q80 || (!k_scales.has_value() && !v_scales.has_value()), name,
+                " takes k_scales / v_scales with an int8 (Q80) KV cache only");
+    TORCH_CHECK(f16 || (k_scales.has_value() && v_scales.has_value()), name,
+                ": an int8 (Q80) KV cache needs k_scales= and v_scales=");
+    const KVScales sc = kv_scales(kc, vc, k_scales, v_scales);
     TORCH_CHECK(head_dim == 64 || head_dim == 128, name,
                 " serves head_dim 64 and 128 (got ", head_dim, "): use ", other);
     TORCH_CHECK(kv_mul >= 1 && kv_mul <= GQA_HEADS, name, " serves kv_mul 1..",
@@ -2137,18 +2263,26 @@ static void attn_gqa_launch(const char *name, const char *other,
     int8_t *zqp = quant ? zq->data_ptr<int8_t>() : nullptr;
     float *zsp = quant ? zs->data_ptr<float>() : nullptr;
     float *zbsp = quant ? zbs->data_ptr<float>() : nullptr;
-    const __half *kcp = reinterpret_cast<__half *>(kc.data_ptr<at::Half>());
-    const __half *vcp = reinterpret_cast<__half *>(vc.data_ptr<at::Half>());
     with_head_vec(head_dim, [&](auto vec_const) {
         constexpr int V = decltype(vec_const)::value;
-        hipLaunchKernelGGL((k_attn_gqa<V, __half, ROWS>),
-                           dim3(n_heads0 / kv_mul, batch, splits),
-                           dim3(GQA_NW * WAVE), 0, cur_stream(),
-                           q.data_ptr<float>(), (int)q_ld, kcp, vcp, rows,
-                           (int)n_heads0, (int)kv_mul, (int)kc.size(1),
-                           1.0f / sqrtf((float)head_dim),
-                           ml_scratch.data_ptr<float>(),
-                           o_scratch.data_ptr<float>());
+        with_kv_ptrs(kc, vc, [&](auto *kcp, auto *vcp) {
+            using KVT = std::remove_pointer_t<decltype(kcp)>;
+            auto launch = [&](auto krows) {
+                hipLaunchKernelGGL((k_attn_gqa<V, KVT, decltype(krows)>),
+                                   dim3(n_heads0 / kv_mul, batch, splits),
+                                   dim3(GQA_NW * WAVE), 0, cur_stream(),
+                                   q.data_ptr<float>(), (int)q_ld, kcp, vcp,
+                                   krows, (int)n_heads0, (int)kv_mul,
+                                   (int)kc.size(1),
+                                   1.0f / sqrtf((float)head_dim),
+                                   ml_scratch.data_ptr<float>(),
+                                   o_scratch.data_ptr<float>());
+            };
+            if constexpr (kKVQ80<KVT>)
+                launch(Q80Rows<ROWS>{rows, sc.k, sc.v});
+            else if constexpr (std::is_same_v<KVT, __half>)
+                launch(rows);
+        });
         combine_launch<V>(ml_scratch, o_scratch, yp, zqp, zsp, zbsp, batch,
                           n_heads0, splits);
     });

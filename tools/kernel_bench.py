@@ -105,57 +105,92 @@ def chunk_ab(positions=(512, 2048, 4096, 8192), batches=(32,), rounds=3,
                   + f"  max |dcode| {diff}")
 
 
-def gqa_ab(positions=(512, 2048, 4096, 8192), batches=(1, 8, 32), rounds=5,
-           gqa_splits=(4, 8, 16, 32)):
+def gqa_ab(kv_dtype="f16", page_size=0, positions=(512, 2048, 4096, 8192),
+           batches=(1, 8, 32), rounds=5, gqa_splits=(4, 8, 16, 32)):
     """Decode-row attention alone in an isolated hipGraph at the 8B shape (32
-    heads, kv_mul 4, hd 128, f16 KV, Q80 output): B rows of B distinct
-    sequences, all at position p. k_attn_split + combine (attn_rows) at the
-    decode schedule's S against k_attn_gqa + combine (attn_gqa_rows) at the
-    same S and at every S of gqa_splits, interleaved over `rounds`: median
+    heads, kv_mul 4, hd 128, Q80 output): B rows of B distinct sequences, all
+    at position p. k_attn_split + combine (attn_rows, or attn_paged with
+    --page-size: pages mapped in a scrambled order) at the decode schedule's S
+    against k_attn_gqa + combine on the same cache at the same S and at every
+    S of gqa_splits, and with --kv-dtype q80 against the f16 k_attn_gqa on
+    the dequantised values (unpaged), interleaved over `rounds`: median
     (min..max) us per call, the fraction of 6.3 TB/s that the distinct K/V
-    bytes reach at the schedule's S, and the largest |code| difference
-    between the two Q80 outputs there.
+    bytes (codes and scales) reach at the schedule's S, and the largest |code|
+    difference between the Q80 outputs of the first two there.
 
-      python tools/kernel_bench.py gqa"""
+      python tools/kernel_bench.py gqa
+      python tools/kernel_bench.py gqa --kv-dtype q80 [--page-size 64]"""
     H0, hd, kvd, kv_mul = 32, 128, 1024, 4
+    P, q80 = page_size, kv_dtype == "q80"
     seq = max(positions) + 64
-    print("\n-- decode-row attention, isolated graph, 8B shape, f16 KV, Q80 out "
+    assert seq % (P or 1) == 0, "a sequence is whole pages"
+    print(f"\n-- decode-row attention, isolated graph, 8B shape, {kv_dtype} KV"
+          f"{f', pages of {P}' if P else ''}, Q80 out "
           "(us per call: median (min..max)) --")
     for B in batches:
-        kc = (torch.randn(B * seq, kvd, device=dev, generator=g) * 0.3).half()
-        vc = torch.randn(B * seq, kvd, device=dev, generator=g).half()
+        n = B * seq
+        if q80:
+            flat = [torch.randint(-127, 128, (n, kvd), device=dev, generator=g)
+                    .to(torch.int8) for _ in range(2)]
+            flat += [(a / 127 * (0.5 + torch.rand(n, kvd // 32, device=dev,
+                                                  generator=g))).half()
+                     for a in (0.3, 1.0)]
+            f16 = [(c.float() * s.float().repeat_interleave(32, dim=1)).half()
+                   for c, s in zip(flat[:2], flat[2:])]
+        else:
+            flat = [(torch.randn(n, kvd, device=dev, generator=g) * 0.3).half(),
+                    torch.randn(n, kvd, device=dev, generator=g).half()]
+        planes, where, form = flat, (), "_rows"
+        if P:  # pool row perm[j] * P + i holds flat row j * P + i
+            perm = torch.randperm(n // P, device=dev, generator=g)
+            src = (perm.argsort()[:, None] * P
+                   + torch.arange(P, device=dev)).reshape(-1)
+            planes = [t[src] for t in flat]
+            where = (perm.to(torch.int32).reshape(B, -1).contiguous(), P)
+            form = "_paged"
+        kw = dict(zip(("k_scales", "v_scales"), planes[2:]))
         qv = torch.randn(B, H0 * hd, device=dev, generator=g)
         y = torch.zeros(B, H0 * hd, device=dev)
         z = [[torch.zeros(B, H0 * hd, dtype=torch.int8, device=dev),
               torch.zeros(B, H0 * hd // 32, device=dev),
               torch.zeros(B, H0 * hd // 32, device=dev)] for _ in range(2)]
         for p in positions:
-            rows = torch.tensor([[b * seq, p] for b in range(B)],
-                                dtype=torch.int32, device=dev)
+            def i32(x):
+                return torch.tensor(x, dtype=torch.int32, device=dev)
+            rows = i32([[b * seq // (P or 1), p] for b in range(B)])
+            flat_rows = i32([[b * seq, p] for b in range(B)])
             S0 = 8 if p < 512 else 16 if p < 2048 else 32
             cands = {}
             for name, S in [("split", S0), ("gqa", S0)] + [
-                    (f"gqa S={S}", S) for S in gqa_splits if S != S0]:
+                    (f"gqa S={S}", S) for S in gqa_splits if S != S0] + [
+                    ("gqa f16", S0)] * q80:
                 ml = torch.zeros(B * H0 * S * 2, device=dev)
                 osc = torch.zeros(B * H0 * S * hd, device=dev)
-                fn = k.attn_rows if name == "split" else k.attn_gqa_rows
-                cands[name] = (lambda fn=fn, S=S, ml=ml, osc=osc, zz=z[
-                    name != "split"]: fn(qv, H0 * hd, kc, vc, y, rows, B, H0,
-                                         kv_mul, hd, S, ml, osc, *zz))
+                tail = (B, H0, kv_mul, hd, S, ml, osc, *z[name != "split"])
+                if name == "gqa f16":
+                    cands[name] = lambda tail=tail: k.attn_gqa_rows(
+                        qv, H0 * hd, *f16, y, flat_rows, *tail)
+                    continue
+                fn = getattr(k, ("attn" if name == "split" else "attn_gqa")
+                             + form)
+                cands[name] = lambda fn=fn, tail=tail: fn(
+                    qv, H0 * hd, *planes[:2], y, rows, *where, *tail, **kw)
             t = {name: [] for name in cands}
             for _ in range(rounds):
                 for name, fn in cands.items():
                     t[name].append(bench(fn, n=16, reps=3))
             cands["split"](), cands["gqa"]()
             diff = (z[0][0].int() - z[1][0].int()).abs().max().item()
-            nbytes = B * (p + 1) * kvd * 2 * 2  # distinct K and V bytes
+            # distinct K and V bytes: codes and scales, or halves
+            nbytes = B * (p + 1) * kvd * 2 * (1 + 2 / 32 if q80 else 2)
             tbs = nbytes / statistics.median(t["gqa"]) / 1e6
             print(f"B={B:2d} pos={p:5d} S={S0:2d}  " + "  ".join(
                 f"{name}: {statistics.median(v):6.1f} ({min(v):.1f}..{max(v):.1f})"
                 for name, v in t.items())
                 + f"  gqa {tbs:4.2f} TB/s ({100 * tbs / 6.3:2.0f}% of 6.3)"
-                f"  max |dcode| {diff}")
-        del kc, vc
+                f"  max |dcode| {diff}", flush=True)
+        del flat, planes
+        f16 = None
 
 
 def chunk_forms_ab(kv_dtype="f16", page_size=0, positions=(512, 2048, 4096, 8192),
@@ -385,13 +420,21 @@ def stream_ab(rounds=3, batches=(8, 16, 32), sweep=False):
 if sys.argv[1:] == ["attn"]:
     attn_ab()
     sys.exit(0)
-if sys.argv[1:2] in (["chunk"], ["chunk-rows"]) and len(sys.argv) > 2:
+if sys.argv[1:2] in (["chunk"], ["chunk-rows"], ["gqa"]) and len(sys.argv) > 2:
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("mode")
     ap.add_argument("--kv-dtype", choices=("f16", "q80"), default="f16")
     ap.add_argument("--page-size", type=int, default=0)
+    ap.add_argument("--batches", default="1,8,32", help="gqa only")
+    ap.add_argument("--positions", default="512,2048,4096,8192",
+                    help="gqa only")
     a = ap.parse_args()
+    if a.mode == "gqa":
+        gqa_ab(a.kv_dtype, a.page_size,
+               tuple(int(p) for p in a.positions.split(",")),
+               tuple(int(b) for b in a.batches.split(",")))
+        sys.exit(0)
     rows = (dict(positions=(512, 4096), batches=(4, 8, 16, 32))
             if a.mode == "chunk-rows" else {})
     chunk_forms_ab(a.kv_dtype, a.page_size, **rows)
