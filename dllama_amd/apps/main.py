@@ -57,6 +57,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "f16 block scales, 0.53x the bytes of f16. CPU "
                         "backend: q80 round-trips K/V through Q80 blocks on "
                         "their way into the f32 cache (the HIP oracle)")
+    p.add_argument("--prefill-rows", type=int, default=0,
+                   choices=[0, 64, 96, 128],
+                   help="HIP backend, one GPU, one slot: feed prompts in chunks "
+                        "of up to this many tokens through the LDS-tiled GEMM "
+                        "and the wide chunk attention (dense models, f16 or "
+                        "q80 KV cache); 0 (default) keeps 32-token chunks")
     p.add_argument("--steps", type=int, default=64)
     p.add_argument("--buffer-float-type", default="q80", choices=["q80", "f32"],
                    help="TP sync buffer quantization (reference --buffer-float-type)")
@@ -129,6 +135,17 @@ def load_engine(args):
     kv_dtype = getattr(args, "kv_dtype", None)
     if kv_dtype is not None:  # the default passes nothing to the backend
         paging["kv_dtype"] = kv_dtype
+    # wide prefill is the HIP backend's; the model refuses what it does not
+    # serve (MoE, tensor parallelism, an f32 or paged cache) with the reason
+    wide = getattr(args, "prefill_rows", 0)
+    if wide and slots > 1:
+        # several slots step through BatchEngine's row steps, which never
+        # reach forward_prefill: the wide buffers would only take memory
+        raise SystemExit(
+            f"error: --prefill-rows {wide} serves the single-sequence path "
+            f"(--slots is {slots}): multi-slot prompts go through row steps "
+            "of at most 32 rows")
+    wide = {"prefill_rows": wide} if wide else {}
     sync = Q80 if args.buffer_float_type == "q80" else F32
     m = mf.ModelFile(args.model, max_seq_len=args.max_seq_len, sync_type=sync)
     use_gpu = torch.cuda.is_available() and args.gpu_index != -1
@@ -142,7 +159,7 @@ def load_engine(args):
             else int(os.environ.get("LOCAL_RANK", "0"))
         model = HipTransformer.from_file(m, cfg, device=f"cuda:{dev}", comm=comm,
                                          n_batches=args.n_batches,
-                                         n_slots=slots, **paging)
+                                         n_slots=slots, **paging, **wide)
         # fused temperature/top-p sampler in the captured decode step; read
         # before the capture, which is what puts it into the graph.
         # DLLAMA_DEVICE_SAMPLER=0 keeps sampling in Sampler.sample_torch

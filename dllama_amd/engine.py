@@ -95,23 +95,31 @@ class InferenceEngine:
 
     def prefill(self, tokens: list[int], start_pos: int | None = None) -> torch.Tensor:
         """Feed prompt tokens in chunks of n_batches; returns logits of the
-        last token [vocab]."""
+        last token [vocab]. A model with prefill_rows > 0 takes chunks of up
+        to prefill_rows through forward_prefill while more than 32 tokens
+        remain."""
         if start_pos is not None:
             self.pos = start_pos
         logits = None
-        starts = list(range(0, len(tokens), self.n_batches))
-        for i in starts:
-            chunk = tokens[i: i + self.n_batches]
-            t = torch.tensor(chunk, dtype=torch.int64)
-            p = torch.arange(self.pos, self.pos + len(chunk), dtype=torch.int64)
+        wide = getattr(self.model, "prefill_rows", 0)
+        i = 0
+        while i < len(tokens):
+            left = len(tokens) - i
+            step = self.model.forward
+            rows = min(left, self.n_batches)
+            if wide and left > 32:
+                step, rows = self.model.forward_prefill, min(left, wide)
+            t = torch.tensor(tokens[i: i + rows], dtype=torch.int64)
+            p = torch.arange(self.pos, self.pos + rows, dtype=torch.int64)
             # intermediate prefill chunks don't need logits (the reference
             # computes them anyway; real serving shouldn't)
-            self.model.skip_logits = i != starts[-1]
+            self.model.skip_logits = i + rows < len(tokens)
             try:
-                logits = self.model.forward(t, p)
+                logits = step(t, p)
             finally:
                 self.model.skip_logits = False
-            self.pos += len(chunk)
+            self.pos += rows
+            i += rows
         return logits[-1]
 
     def decode_one(self, token: int) -> torch.Tensor:

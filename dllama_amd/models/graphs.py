@@ -4,6 +4,7 @@ A graph is valid for what its key names, at the `attn_splits` it was
 captured at (its launches name the split scratch; a change: `clear()`):
     ("decode", logprobs)      the B=1 step; its note: it ends in the sampler
     ("prefill", skip_logits)  a full prompt chunk
+    ("prefill_wide", skip_logits)  a full chunk of prefill_rows rows
     ("rows", B, logprobs)     an all-decode row step of B rows
 A step comes as a plan: a callable that creates the buffers the step needs
 and returns `(body, warmups, tail, note)`. The store holds no tensors.

@@ -41,6 +41,7 @@ from __future__ import annotations
 import os
 import sys
 from functools import partial
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -167,7 +168,7 @@ class HipTransformer:
     def __init__(self, config: ModelConfig, device=None, comm: Comm | None = None,
                  n_batches: int = 32, force_sync: bool = False,
                  n_slots: int = 1, kv_pages: int = 0, page_size: int = 64,
-                 kv_dtype: str | None = None):
+                 kv_dtype: str | None = None, prefill_rows: int = 0):
         self.cfg = c = config
         if kv_dtype not in (None, "f16", "f32", "q80"):
             raise ValueError(
@@ -246,7 +247,15 @@ class HipTransformer:
             # a Q80 block: the QKV GEMV + rope_kv pair runs instead (one more
             # launch per layer for a single llama sequence)
             self.fused_rope = False
+        # wide prefill (forward_prefill, docs/DESIGN.md §14): a second set of
+        # step buffers of prefill_rows rows; the keyword wins over
+        # DLLAMA_PREFILL_ROWS. 0: nothing of it is allocated or launched
+        self.prefill_rows = prefill_rows or self.prefill_rows
+        self._check_prefill_rows()
+        self.wide = None
         self._alloc_buffers()
+        if self.prefill_rows:
+            self._alloc_wide()
 
     def _read_options(self):
         """Every DLLAMA_* option of the model, read once per construction."""
@@ -332,6 +341,9 @@ class HipTransformer:
         # profiles/r16_stream_gemm.md); set_stream_gemm on a live model
         self.stream_gemm = flag("DLLAMA_GEMM_STREAM", "0")
         self.stream_gemm_min_rows = 8  # where _mm leaves the GEMV
+        # prompt chunks of up to this many rows through forward_prefill
+        # (q40_gemm_tile + attn_chunk_wide); the constructor's keyword wins
+        self.prefill_rows = int(env.get("DLLAMA_PREFILL_ROWS", "0"))
         # deferred-quant dense decode (EPI_RESID_Q + PRO2); =0 reverts to
         # explicit norm_quant launches
         self.use_deferred = flag("DLLAMA_DEFERRED", "1")
@@ -357,7 +369,8 @@ class HipTransformer:
                   force_sync: bool = False,
                   n_slots: int = 1, kv_pages: int = 0,
                   page_size: int = 64,
-                  kv_dtype: str | None = None) -> "HipTransformer":
+                  kv_dtype: str | None = None,
+                  prefill_rows: int = 0) -> "HipTransformer":
         from ..quants import Q40
         if m.header.weight_type != Q40:
             raise ValueError(
@@ -365,7 +378,7 @@ class HipTransformer:
                 "shipped format); f32/q80 .m files run on the CPU backend "
                 "(--gpu-index -1) or can be re-quantized with convert_hf.py")
         self = cls(config, device, comm, n_batches, force_sync, n_slots,
-                   kv_pages, page_size, kv_dtype)
+                   kv_pages, page_size, kv_dtype, prefill_rows)
         c, dev = config, self.device
         r, w = c.rank, c.world
 
@@ -418,11 +431,12 @@ class HipTransformer:
                   force_sync: bool = False,
                   n_slots: int = 1, kv_pages: int = 0,
                   page_size: int = 64,
-                  kv_dtype: str | None = None) -> "HipTransformer":
+                  kv_dtype: str | None = None,
+                  prefill_rows: int = 0) -> "HipTransformer":
         """Random-init weights built directly on device (benches: no network
         for checkpoints, and an 8B .m file round-trip is pointless there)."""
         self = cls(config, device, comm, n_batches, force_sync, n_slots,
-                   kv_pages, page_size, kv_dtype)
+                   kv_pages, page_size, kv_dtype, prefill_rows)
         c, dev = config, self.device
         gen = torch.Generator(device=dev)
         gen.manual_seed(seed + c.rank)
@@ -523,6 +537,49 @@ class HipTransformer:
         n = self.n_batches * c.n_heads0 * self.attn_splits
         self.attn_ml = torch.zeros(n * 2, device=dev)
         self.attn_o = torch.zeros(n * c.head_dim, device=dev)
+        if self.wide is not None:
+            n = self.prefill_rows * c.n_heads0 * self.attn_splits
+            self.wide.attn_ml = torch.zeros(n * 2, device=dev)
+            self.wide.attn_o = torch.zeros(n * c.head_dim, device=dev)
+
+    def _check_prefill_rows(self):
+        """prefill_rows is 0 or a chunk size the wide path serves, on a model
+        it serves (docs/DESIGN.md §14, "Not done")."""
+        c, rows = self.cfg, self.prefill_rows
+        if not rows:
+            return
+        if rows not in (64, 96, 128):
+            raise ValueError(
+                f"prefill_rows must be 0, 64, 96 or 128 (got {rows})")
+        why = ("MoE models: the expert matmuls have no tiled form"
+               if c.is_moe else
+               "the tensor-parallel path (world > 1 or force_sync)"
+               if self.tp_path else
+               'kv_dtype="f32": the chunk attention reads f16 or Q80 caches'
+               if self.kv_f32 else
+               f"head_dim {c.head_dim}: the chunk attention has 64 and 128"
+               if c.head_dim not in (64, 128) else
+               "a paged KV cache: a paged model steps rows only"
+               if self.kv_pages else None)
+        if why:
+            raise ValueError(f"prefill_rows does not serve {why}")
+
+    def _alloc_wide(self):
+        """The step buffers of forward_prefill, prefill_rows rows each. No
+        [rows, vocab] logits: only the last row's are computed, into
+        logits0[:1] through the narrow xq."""
+        c, dev, rows = self.cfg, self.device, self.prefill_rows
+        w = self.wide = SimpleNamespace()
+        w.tokens = torch.zeros(rows, dtype=torch.int64, device=dev)
+        w.x = torch.zeros(rows, c.dim, device=dev)
+        w.xq = QuantBuf(rows, c.dim, dev)
+        w.qkv_out = torch.zeros(rows, self.qkv_ld, device=dev)
+        w.zbuf = torch.zeros(rows, c.q_dim0, device=dev)
+        w.zq = QuantBuf(rows, c.q_dim0, dev)
+        w.ff_out = torch.zeros(rows, 2 * c.ff_dim0, device=dev)
+        w.dq = QuantBuf(rows, c.ff_dim0, dev)
+        w.ssq = torch.zeros(2 * c.n_layers + 1, rows, 16 * 32, device=dev)
+        self._alloc_attn_scratch()
 
     def _dequant_bf16(self, lin: Linear) -> torch.Tensor:
         """Q40 planes -> bf16 weight matrix on device (prefill GEMM shadow;
@@ -628,15 +685,18 @@ class HipTransformer:
                              self.k_cache[l], self.v_cache[l], c.q_dim0,
                              c.kv_dim0, c.head_dim, **deferred)
 
-    def _qknorm_rope_kv(self, l: int, lw: dict, B: int, addr: KVAddr):
-        """Per-head q/k rmsnorm (qwen3), rope and KV write on qkv_out, for
-        the schedules whose QKV matmul has no rope epilogue."""
+    def _qknorm_rope_kv(self, l: int, lw: dict, B: int, addr: KVAddr,
+                        qkv=None):
+        """Per-head q/k rmsnorm (qwen3), rope and KV write on qkv_out (or the
+        wide step's `qkv`), for the schedules whose QKV matmul has no rope
+        epilogue."""
         c, k = self.cfg, self.k
+        qkv = self.qkv_out if qkv is None else qkv
         if c.is_qwen3 and self.rope_style == 1:
             # one launch (replaces 2x rmsnorm_rows_s + rope_kv = ~9 us/layer
             # of launch overhead in the captured graph)
             getattr(k, addr.rope_kv_qknorm)(
-                self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0,
+                qkv, self.qkv_ld, c.q_dim0, c.kv_dim0,
                 self.rope_cache, *addr.where, self.k_cache[l],
                 self.v_cache[l], c.head_dim, lw["q_norm"], lw["k_norm"],
                 c.norm_eps, B, **self._kv_scales(l))
@@ -644,11 +704,11 @@ class HipTransformer:
         if c.is_qwen3:
             for col0, width, wn in ((0, c.q_dim0, lw["q_norm"]),
                                     (c.q_dim0, c.kv_dim0, lw["k_norm"])):
-                k.rmsnorm_rows_s(self.qkv_out, self.qkv_ld, col0,
+                k.rmsnorm_rows_s(qkv, self.qkv_ld, col0,
                                  width // c.head_dim, B, wn, c.head_dim,
                                  c.norm_eps)
         getattr(k, addr.rope_kv)(
-            self.qkv_out, self.qkv_ld, c.q_dim0, c.kv_dim0, self.rope_cache,
+            qkv, self.qkv_ld, c.q_dim0, c.kv_dim0, self.rope_cache,
             *addr.where, self.k_cache[l], self.v_cache[l], c.head_dim,
             self.rope_style, B, **self._kv_scales(l))
 
@@ -1147,6 +1207,81 @@ class HipTransformer:
             self.k.logits_concat(self.logits_full, self.logits_gather[NBp], B)
             return self.logits_full[:B]
         return self.logits0[:B]
+
+    def forward_prefill(self, tokens: torch.Tensor, positions: torch.Tensor):
+        """A prompt chunk of 33..prefill_rows consecutive rows of the single
+        sequence through the wide buffers (docs/DESIGN.md §14). Returns the
+        last row's logits [1, vocab], or None under skip_logits. A full chunk
+        replays a captured graph, a partial one runs eager. Leaves `pos` and
+        the decode graph's ownership as _step_at does."""
+        if self.wide is None:
+            raise ValueError("forward_prefill needs a model built with "
+                             "prefill_rows=64, 96 or 128")
+        B = tokens.shape[0]
+        if not 32 < B <= self.prefill_rows:
+            raise ValueError(
+                f"forward_prefill takes 33..{self.prefill_rows} rows (got "
+                f"{B}): up to 32 rows go through forward")
+        p0 = self._first_position(positions, B)
+        self.wide.tokens[:B].copy_(tokens.to(self.device), non_blocking=True)
+        self._follow_wide_tier(p0 + B - 1, emit_q80=True)
+        # before a capture too: its warmup writes the KV rows of the chunk
+        self.pos.fill_(p0)
+        self._graph_pos = None  # the decode graph no longer owns the position
+        g = None
+        if B == self.prefill_rows:
+            g = self.graphs.get(("prefill_wide", self.skip_logits), lambda: (
+                lambda: self._forward_wide(B), 1, None, None))
+        if g is not None:
+            g.replay()
+        else:
+            self._forward_wide(B)
+        return None if self.skip_logits else self.logits0[:1]
+
+    def _forward_wide(self, B: int):
+        """The explicit-norm schedule of _forward_explicit over B rows of the
+        wide buffers: every dense matmul is q40_gemm_tile (wo and w2 its
+        residual form), attention is attn_chunk_wide whatever the chunk
+        option says, rope / qk-norm / KV write are the single-sequence
+        launches at B rows. Logits: the last row only, final norm into the
+        narrow xq and the wcls GEMV into logits0[:1]."""
+        c, k, w = self.cfg, self.k, self.wide
+        f = c.ff_dim0
+        gelu = c.hidden_act == HIDDEN_ACT_GELU
+
+        def norm_mm(lin, wn, slot, out):
+            k.norm_quant(w.x[:B], wn, w.ssq[slot], *w.xq.triple(B), B,
+                         c.norm_eps)
+            k.q40_gemm_tile(lin.qs, lin.scales, *w.xq.triple(B), out, B)
+
+        def proj_merge(lin, qb, slot):
+            k.q40_gemm_tile_resid(lin.qs, lin.scales, *qb.triple(B), w.x,
+                                  w.ssq[slot], B)
+
+        w.ssq.zero_()
+        k.embed_gather(self.embedding, w.tokens, w.x, B, w.ssq[0])
+        slot = 0
+        for l, lw in enumerate(self.layers):
+            norm_mm(lw["qkv"], lw["norm0"], slot, w.qkv_out)
+            self._qknorm_rope_kv(l, lw, B, self.seq_addr, w.qkv_out)
+            k.attn_chunk_wide(
+                w.qkv_out, self.qkv_ld, self.k_cache[l], self.v_cache[l],
+                w.zbuf[:B], self.pos, B, c.n_heads0, self.kv_mul, c.head_dim,
+                self.attn_splits, w.attn_ml, w.attn_o, *w.zq.triple(),
+                **self._kv_scales(l))
+            proj_merge(lw["wo"], w.zq, slot + 1)
+            slot += 1
+            norm_mm(lw["w13"], lw["norm1"], slot, w.ff_out)
+            k.swiglu_q80(w.ff_out, w.ff_out[:, f:], 2 * f, f, B,
+                         *w.dq.triple(B), gelu)
+            proj_merge(lw["w2"], w.dq, slot + 1)
+            slot += 1
+        if self.skip_logits:
+            return
+        k.norm_quant(w.x[B - 1:B], self.final_norm, w.ssq[slot][B - 1:],
+                     *self.xq.triple(1), 1, c.norm_eps)
+        k.q40_gemv(self.wcls.qs, self.wcls.scales, *self.xq.triple(),
+                   self.logits0, 1)
 
     def _first_position(self, positions, B: int) -> int:
         """positions[0] of a single-sequence step of B rows, checked."""

@@ -20,6 +20,16 @@ struct SeqRows {
     __device__ int64_t cache_base(int) const { return 0; }
     __device__ int64_t cache_row(int, int t) const { return t; }
 };
+// WideRows: SeqRows for a prompt chunk of more than 32 rows. The rows are
+// placed as SeqRows places them; the type tells k_attn_chunk to cut the one
+// sequence into runs itself: run y is rows 32y .. min(32y + 31, batch - 1).
+struct WideRows {
+    static constexpr bool kPaged = false;
+    const int *pos;
+    __device__ int position(int b) const { return pos[0] + b; }
+    __device__ int64_t cache_base(int) const { return 0; }
+    __device__ int64_t cache_row(int, int t) const { return t; }
+};
 // TableRows: int32 [B, 2] = {cache_row_base, pos} per row, cache_row_base =
 // slot * seq_len: row b is position pos of the sequence whose cache rows
 // start at cache_row_base. Expresses N sequences decoding together, a prompt
@@ -831,7 +841,11 @@ k_attn_chunk(const float *__restrict__ q, int q_ld,
     // the run: SeqRows = the whole batch; a table run is clamped to the batch
     // and to the tile, so a bad table cannot send a load or store astray
     int b0 = 0, n = batch;
-    if constexpr (!std::is_base_of_v<SeqRows, ROWS>) {
+    if constexpr (std::is_base_of_v<WideRows, ROWS>) {
+        // the host launches ceil(batch / 32) runs: b0 < batch
+        b0 = min((int)blockIdx.y * CHUNK_ROWS, batch - 1);
+        n = batch - b0;
+    } else if constexpr (!std::is_base_of_v<SeqRows, ROWS>) {
         b0 = min(max(runs[2 * blockIdx.y], 0), batch - 1);
         n = min(runs[2 * blockIdx.y + 1], batch - b0);
     }
@@ -2166,6 +2180,29 @@ void attn_chunk(torch::Tensor q, int64_t q_ld, torch::Tensor kc,
                       zbs, k_scales, v_scales);
 }
 
+// attn_chunk for 1..128 rows of one sequence: ceil(batch / 32) runs in one
+// launch, cut by the kernel (WideRows); each run's workgroups walk only the
+// tiles below that run's longest row. The scratch holds batch * n_heads0 *
+// splits partials. (attn_chunk itself keeps refusing more than one run.)
+void attn_chunk_wide(torch::Tensor q, int64_t q_ld, torch::Tensor kc,
+                     torch::Tensor vc, torch::Tensor y, torch::Tensor pos,
+                     int64_t batch, int64_t n_heads0, int64_t kv_mul,
+                     int64_t head_dim, int64_t splits, torch::Tensor ml_scratch,
+                     torch::Tensor o_scratch, OptTensor zq = c10::nullopt,
+                     OptTensor zs = c10::nullopt, OptTensor zbs = c10::nullopt,
+                     OptTensor k_scales = c10::nullopt,
+                     OptTensor v_scales = c10::nullopt) {
+    TORCH_CHECK(batch >= 1 && batch <= 4 * CHUNK_ROWS,
+                "attn_chunk_wide takes 1..128 rows of one sequence");
+    TORCH_CHECK(q.numel() >= (batch - 1) * q_ld + n_heads0 * head_dim,
+                "attn_chunk_wide: q shorter than `batch` rows");
+    attn_chunk_launch("attn_chunk_wide", "attn", q, q_ld, kc, vc, y,
+                      WideRows{pos.data_ptr<int>()}, nullptr,
+                      ceil_div(batch, CHUNK_ROWS), batch, n_heads0, kv_mul,
+                      head_dim, splits, ml_scratch, o_scratch, zq, zs, zbs,
+                      k_scales, v_scales);
+}
+
 // A run table as the kernel reads it: int32 [>= n_runs, 2] = {first batch
 // row, row count}, each run consecutive rows of one sequence.
 static const int *run_table(const torch::Tensor &runs, int64_t n_runs,
@@ -2559,6 +2596,13 @@ void register_attn(py::module &m) {
           py::arg("ml_scratch"), py::arg("o_scratch"),
           py::arg("zq") = py::none(), py::arg("zs") = py::none(),
           py::arg("zbs") = py::none(), KV_SCALE_ARGS);
+    m.def("attn_chunk_wide", &attn_chunk_wide, py::arg("q"), py::arg("q_ld"),
+          py::arg("kc"), py::arg("vc"), py::arg("y"), py::arg("pos"),
+          py::arg("batch"), py::arg("n_heads0"), py::arg("kv_mul"),
+          py::arg("head_dim"), py::arg("splits"), py::arg("ml_scratch"),
+          py::arg("o_scratch"), py::arg("zq") = py::none(),
+          py::arg("zs") = py::none(), py::arg("zbs") = py::none(),
+          KV_SCALE_ARGS);
     m.def("attn_gqa", &attn_gqa, py::arg("q"), py::arg("q_ld"), py::arg("kc"),
           py::arg("vc"), py::arg("y"), py::arg("pos"), py::arg("batch"),
           py::arg("n_heads0"), py::arg("kv_mul"), py::arg("head_dim"),

@@ -789,6 +789,275 @@ k_q40_gemm_stream(const uint8_t *__restrict__ qs,
     }
 }
 
+// -------------------------------------- LDS-tiled GEMM (prompt chunks, <= 128)
+// The Q40xQ80 product for 1..128 activation rows, built around an activation
+// tile instead of a weight stream (opt-in: prefill_rows, docs/DESIGN.md §14).
+// A workgroup of 8 waves owns RT * 16 weight rows against ALL `batch`
+// activation rows and walks K in chunks of 8 blocks; a chunk of both operands
+// is staged in LDS once and read by every wave, so a weight byte leaves HBM
+// once per call and an activation byte leaves L2 once per workgroup.
+//
+// MFMA, fragment layout, unpack, the -8 * bsum C input and the descale are
+// k_q40_gemm_stream's (v_mfma_i32_16x16x32_i8, weights as A, 16 activation
+// rows as the B columns): sw * sx rounded once, one f32 fma per block into the
+// accumulator, in block order. No K split at all: one wave sums all n / 32
+// blocks of its C tiles, so a row's bits depend on nothing but (n, the row).
+//
+// Work split, from (d, n) alone: RT = 1 (16 weight rows) below d = 6144, so
+// that d = 4096 still launches 256 workgroups, RT = 2 from there. The 8 waves
+// split the C tile, not K: wave w owns row tile w / (8 / RT) and the RT
+// column tiles w % (8 / RT) + u * (8 / RT). `batch` enters only as the number
+// of live 16-column tiles nt = ceil(batch / 16): a wave skips the MFMAs of a
+// tile at or past nt, and LDS holds nt code tiles.
+//
+// LDS, per stage (two stages, dwords): weight tile RT * 512, code tiles
+// nt * 1024, weight scales as f32 RT * 128, {sx, -8 bsum} nt * 256; in all
+// 2 * (2.5 RT + 5 nt) KiB: 85 KiB at RT = 1 and 90 KiB at RT = 2 for 128 rows
+// (one workgroup = 2 waves per SIMD on a CU of 160 KiB), 45 / 50 KiB for 64
+// rows. There LDS would hold three workgroups but the registers decide: at
+// 120..122 VGPRs (RT = 1) a SIMD holds 4 waves, two workgroups per CU; at
+// 138..140 (RT = 2) it holds 3, which is one workgroup of 2 waves per SIMD
+// again. Both tiles use §12's XOR swizzle unchanged: 8 lanes
+// write the 8 blocks of one weight row (one 128-byte line) as b128, 16 lanes
+// the 16 uint4 of one column's chunk; the b32 fragment reads touch every bank
+// once. The tiles are shared now, so the K loop has one barrier per chunk:
+// chunk c + 1 is loaded into registers before chunk c's MFMAs and written to
+// the other stage after them.
+//
+// Edges as §12: rows at or past d are clamped for loads and masked at the
+// store; columns at or past `batch` are staged as zeros and form no address;
+// blocks at or past n / 32 are neither loaded nor multiplied.
+//
+// GT_PLAIN stores f32 y[b][row]; GT_RESID adds into x[b][row] in place and
+// adds the column's squares, summed over the workgroup's rows, with one atomic
+// per column into ssq_slot(b, blockIdx.x). `vec4`: d % 4 == 0 and a 16-byte
+// aligned output, so a lane's four consecutive rows go as one 16-byte access.
+enum { GT_PLAIN = 0, GT_RESID = 1 };
+#define GT_CHUNK 8
+#define GT_WAVES 8
+#define GT_MAX_ROWS 128
+
+// dwords of one LDS stage with nt live 16-column tiles
+static constexpr int gt_stage_dwords(int RT, int nt) {
+    return RT * 512 + nt * 1024 + RT * 128 + nt * 256;
+}
+
+template <int RT, int EPI>
+__global__ void __launch_bounds__(GT_WAVES * WAVE)
+k_q40_gemm_tile(const uint8_t *__restrict__ qs,
+                const __half *__restrict__ scales,
+                const int8_t *__restrict__ xq,
+                const float *__restrict__ xs,
+                const float *__restrict__ xbs,
+                float *__restrict__ y,    // GT_RESID: the residual x
+                float *__restrict__ ssq,  // GT_RESID only
+                int d, int n, int batch, int vec4) {
+    extern __shared__ uint32_t gt_lds[];
+    constexpr int CG = GT_WAVES / RT;  // waves per row tile
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
+    const int lane = tid % WAVE;
+    const int m = lane & 15;   // fragment row (A) / column (B, C)
+    const int g = lane >> 4;   // k-group; C rows 4g..4g+3
+    const int nt = (batch + 15) >> 4;
+    const int ncols = nt * 16;
+    const int SD = gt_stage_dwords(RT, nt);
+    const int xoff = RT * 512, swoff = xoff + nt * 1024, sboff = swoff + RT * 128;
+    const int nb = n / QB;
+    const int nchunks = (nb + GT_CHUNK - 1) / GT_CHUNK;
+    const int rbase = blockIdx.x * (RT * 16);
+    const int rt = wave / CG;  // this wave's row tile
+    const int cw = wave % CG;  // and its first column tile
+
+    // staging roles. Weights: thread t < RT * 128 takes block t & 7 of row
+    // t >> 3 of every chunk, and that row's scale of the block
+    const int lblk = tid & 7;
+    const int wrow = tid >> 3;
+    const bool wrole = tid < RT * 128;
+    const int grow = min(rbase + min(wrow, RT * 16 - 1), d - 1);
+    const uint4 *wp = reinterpret_cast<const uint4 *>(qs + (int64_t)grow * (n >> 1)) + lblk;
+    const __half *sp = scales + (int64_t)grow * nb + lblk;
+    const int wst = wrow * 32 + ((lblk ^ ((wrow >> 1) & 7)) << 2);
+    // codes: uint4 xu of the chunk of column 32 i + cb; {sx, bsum}: block
+    // lblk of column 64 i + wrow
+    const int xu = tid & 15;
+    const int cb = tid >> 4;
+
+    uint4 wr = make_uint4(0, 0, 0, 0);
+    __half swr = __float2half(0.0f);
+    uint4 xr[4];
+    float sxr[2], bsr[2];
+
+    auto load = [&](int c) {
+        const bool okb = c * GT_CHUNK + lblk < nb;
+        if (wrole) {
+            wr = okb ? wp[c * GT_CHUNK] : make_uint4(0, 0, 0, 0);
+            swr = okb ? sp[c * GT_CHUNK] : __float2half(0.0f);
+        }
+        #pragma unroll
+        for (int i = 0; i < 2; i++) {
+            const int col = i * 64 + wrow;
+            const bool ok = okb && col < batch;
+            const int64_t at = (int64_t)col * nb + c * GT_CHUNK + lblk;
+            sxr[i] = ok ? xs[at] : 0.0f;
+            bsr[i] = ok ? xbs[at] : 0.0f;
+        }
+        const bool oku = c * GT_CHUNK + (xu >> 1) < nb;
+        #pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int col = i * 32 + cb;
+            xr[i] = make_uint4(0, 0, 0, 0);
+            if (oku && col < batch)
+                xr[i] = *reinterpret_cast<const uint4 *>(
+                    xq + (int64_t)col * n + (int64_t)c * (GT_CHUNK * QB) + xu * 16);
+        }
+    };
+    auto stage = [&](int buf) {
+        uint32_t *st = gt_lds + buf * SD;
+        if (wrole) {
+            *reinterpret_cast<gs_uint4 *>(st + wst) = wr;
+            reinterpret_cast<float *>(st + swoff)[lblk * (RT * 16) + wrow] =
+                __half2float(swr);
+        }
+        #pragma unroll
+        for (int i = 0; i < 2; i++) {
+            const int col = i * 64 + wrow;
+            // the code sum is an integer below 2^24: exact in f32 and in int
+            if (col < ncols)
+                *reinterpret_cast<gs_uint2 *>(st + sboff + (lblk * ncols + col) * 2) =
+                    make_uint2(__float_as_uint(sxr[i]), (uint32_t)(-8 * (int)bsr[i]));
+        }
+        #pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int col = i * 32 + cb;
+            const int c16 = col & 15;
+            if (col < ncols)
+                *reinterpret_cast<gs_uint4 *>(
+                    st + xoff + (col >> 4) * 1024 + c16 * 64 + ((xu ^ c16) << 2)) = xr[i];
+        }
+    };
+
+    float acc[RT][4];
+    bool live[RT];
+    #pragma unroll
+    for (int u = 0; u < RT; u++) {
+        live[u] = cw + u * CG < nt;  // wave-uniform
+        #pragma unroll
+        for (int r = 0; r < 4; r++) acc[u][r] = 0.0f;
+    }
+
+    const int wrd = rt * 512 + m * 32 + g;  // weight fragment read, + swizzled block
+    const int wsw = (m >> 1) & 7;
+    const int xrd = xoff + m * 64 + g;      // code fragment read
+    auto block = [&](const uint32_t *st, int jj) {
+        const uint32_t v = st[wrd + ((jj ^ wsw) << 2)];
+        const uint32_t lo = v & 0x0F0F0F0Fu;
+        const uint32_t hi = (v >> 4) & 0x0F0F0F0Fu;
+        const long a = (long)(((uint64_t)hi << 32) | lo);
+        const gs_float4 sw4 = *reinterpret_cast<const gs_float4 *>(
+            reinterpret_cast<const float *>(st + swoff) + jj * (RT * 16) + rt * 16 + 4 * g);
+        const float s4[4] = {sw4.x, sw4.y, sw4.z, sw4.w};
+        #pragma unroll
+        for (int u = 0; u < RT; u++) {
+            if (!live[u]) continue;
+            const int tile = cw + u * CG;
+            const uint32_t x0 = st[tile * 1024 + xrd + (((2 * jj) ^ m) << 2)];
+            const uint32_t x1 = st[tile * 1024 + xrd + (((2 * jj + 1) ^ m) << 2)];
+            const long b = (long)(((uint64_t)x1 << 32) | x0);
+            const gs_uint2 sb = *reinterpret_cast<const gs_uint2 *>(
+                st + sboff + (jj * ncols + tile * 16 + m) * 2);
+            const float sx = __uint_as_float(sb.x);
+            const int off = (int)sb.y;
+            v4i32_t ci = {off, off, off, off};
+            ci = __builtin_amdgcn_mfma_i32_16x16x32_i8(a, b, ci, 0, 0, 0);
+            #pragma unroll
+            for (int r = 0; r < 4; r++)
+                acc[u][r] = fma_f32((float)ci[r], mul_f32(s4[r], sx), acc[u][r]);
+        }
+    };
+
+    load(0);
+    stage(0);
+    __syncthreads();
+    for (int c = 0; c < nchunks; c++) {
+        const uint32_t *st = gt_lds + (c & 1) * SD;
+        const bool more = c + 1 < nchunks;
+        if (more) load(c + 1);
+        const int nblk = min(GT_CHUNK, nb - c * GT_CHUNK);
+        if (nblk == GT_CHUNK) {
+            #pragma unroll
+            for (int jj = 0; jj < GT_CHUNK; jj++) block(st, jj);
+        } else {
+            #pragma unroll 1
+            for (int jj = 0; jj < nblk; jj++) block(st, jj);
+        }
+        // the other stage was last read before the previous barrier
+        if (more) stage((c + 1) & 1);
+        __syncthreads();
+    }
+
+    float sq[RT];
+    const int row0 = rbase + rt * 16 + 4 * g;
+    #pragma unroll
+    for (int u = 0; u < RT; u++) {
+        sq[u] = 0.0f;
+        const int col = (cw + u * CG) * 16 + m;
+        if (!live[u] || col >= batch || row0 >= d) continue;
+        float *at = y + (int64_t)col * d + row0;
+        if (vec4) {
+            gs_float4 *at4 = reinterpret_cast<gs_float4 *>(at);
+            if constexpr (EPI == GT_PLAIN) {
+                *at4 = make_float4(acc[u][0], acc[u][1], acc[u][2], acc[u][3]);
+            } else {
+                gs_float4 xv = *at4;
+                xv.x = add_f32(xv.x, acc[u][0]);
+                xv.y = add_f32(xv.y, acc[u][1]);
+                xv.z = add_f32(xv.z, acc[u][2]);
+                xv.w = add_f32(xv.w, acc[u][3]);
+                *at4 = xv;
+                sq[u] = fma_f32(xv.x, xv.x, sq[u]);
+                sq[u] = fma_f32(xv.y, xv.y, sq[u]);
+                sq[u] = fma_f32(xv.z, xv.z, sq[u]);
+                sq[u] = fma_f32(xv.w, xv.w, sq[u]);
+            }
+        } else {
+            #pragma unroll
+            for (int r = 0; r < 4; r++) {
+                if (row0 + r >= d) continue;
+                if constexpr (EPI == GT_PLAIN) {
+                    at[r] = acc[u][r];
+                } else {
+                    const float xv = add_f32(at[r], acc[u][r]);
+                    at[r] = xv;
+                    sq[u] = fma_f32(xv, xv, sq[u]);
+                }
+            }
+        }
+    }
+    if constexpr (EPI == GT_RESID) {
+        // a column's squares: over the 4 k-groups by shuffle, over the RT row
+        // tiles through LDS (the stages are dead: the K loop ended on a
+        // barrier), one atomic per column and workgroup. Every live column
+        // tile has exactly one wave per row tile.
+        float *sql = reinterpret_cast<float *>(gt_lds);
+        #pragma unroll
+        for (int u = 0; u < RT; u++) {
+            float s = sq[u];
+            s += __shfl_xor(s, 16, WAVE);
+            s += __shfl_xor(s, 32, WAVE);
+            if (live[u] && g == 0)
+                sql[rt * GT_MAX_ROWS + (cw + u * CG) * 16 + m] = s;
+        }
+        __syncthreads();
+        if (tid < batch) {
+            float t = 0.0f;
+            #pragma unroll
+            for (int a = 0; a < RT; a++) t += sql[a * GT_MAX_ROWS + tid];
+            atomicAdd(ssq_slot(ssq, tid, blockIdx.x), t);
+        }
+    }
+}
+
 // ============================================================== host bindings
 
 void q40_gemm(torch::Tensor qs, torch::Tensor scales, torch::Tensor xq,
@@ -984,7 +1253,95 @@ void q40_gemm_stream_resid(torch::Tensor qs, torch::Tensor scales,
                               batch, rows, waves);
 }
 
+// Weight rows per workgroup of the tiled GEMM over a [d, n] matrix, in tiles
+// of 16, from d alone (a row's bits depend on neither): 16 rows keep 256
+// workgroups at d = 4096 (wo, w2), 32 rows halve the activation re-reads from
+// L2 wherever that still leaves more workgroups than CUs.
+static int tile_rt(int d) { return d >= 6144 ? 2 : 1; }
+
+template <int RT, int EPI>
+static void tile_launch(const uint8_t *qs, const __half *sc, const int8_t *xq,
+                        const float *xs, const float *xbs, float *y, float *ssq,
+                        int d, int n, int batch, int vec4) {
+    auto *kern = k_q40_gemm_tile<RT, EPI>;
+    // two stages of 128 rows are 85 / 90 KiB, above the default cap. The
+    // attribute belongs to a device: set once on each device the op meets
+    // (a step's eager warm-up meets it before any graph capture does)
+    static bool set_on[64] = {};
+    int device = 0;
+    TORCH_CHECK(hipGetDevice(&device) == hipSuccess && device >= 0 && device < 64,
+                "tile gemm: no current device");
+    if (!set_on[device]) {
+        const hipError_t attr = hipFuncSetAttribute(
+            reinterpret_cast<const void *>(kern),
+            hipFuncAttributeMaxDynamicSharedMemorySize,
+            2 * gt_stage_dwords(RT, GT_MAX_ROWS / 16) * 4);
+        TORCH_CHECK(attr == hipSuccess, "tile gemm: LDS attribute: ",
+                    hipGetErrorString(attr));
+        set_on[device] = true;
+    }
+    const size_t lds = (size_t)2 * gt_stage_dwords(RT, ceil_div(batch, 16)) * 4;
+    hipLaunchKernelGGL(kern, dim3(ceil_div(d, RT * 16)), dim3(GT_WAVES * WAVE),
+                       lds, cur_stream(), qs, sc, xq, xs, xbs, y, ssq, d, n,
+                       batch, vec4);
+}
+
+template <int EPI>
+static void tile_dispatch(torch::Tensor &qs, torch::Tensor &scales,
+                          torch::Tensor &xq, torch::Tensor &xs,
+                          torch::Tensor &xbs, torch::Tensor &y, float *ssq,
+                          int64_t batch) {
+    CHECK_CUDA(qs); CHECK_CONT(qs); CHECK_CONT(scales); CHECK_CONT(xq);
+    CHECK_CONT(xs); CHECK_CONT(xbs); CHECK_CUDA(y); CHECK_CONT(y);
+    const int d = qs.size(0);
+    const int n = qs.size(1) * 2;
+    TORCH_CHECK(d >= 1 && n >= QB && n % QB == 0, "n must be a multiple of 32");
+    TORCH_CHECK(batch >= 1 && batch <= GT_MAX_ROWS, "tile gemm takes 1..128 rows");
+    TORCH_CHECK(xq.size(-1) == n && xq.numel() >= batch * n
+                && xs.numel() * QB >= batch * n && xbs.numel() * QB >= batch * n,
+                "input triple shorter than [batch, n]");
+    TORCH_CHECK(xs.scalar_type() == torch::kFloat32
+                && xbs.scalar_type() == torch::kFloat32
+                && y.scalar_type() == torch::kFloat32, "xs, xbs and y are f32");
+    TORCH_CHECK(y.numel() >= batch * d, "output shorter than [batch, d]");
+    const int vec4 = d % 4 == 0
+        && reinterpret_cast<uintptr_t>(y.data_ptr<float>()) % 16 == 0;
+    auto go = [&](auto launch) {
+        launch(qs.data_ptr<uint8_t>(),
+               reinterpret_cast<const __half *>(scales.data_ptr<at::Half>()),
+               xq.data_ptr<int8_t>(), xs.data_ptr<float>(), xbs.data_ptr<float>(),
+               y.data_ptr<float>(), ssq, d, n, (int)batch, vec4);
+    };
+    if (tile_rt(d) == 1) go(tile_launch<1, EPI>);
+    else go(tile_launch<2, EPI>);
+}
+
+void q40_gemm_tile(torch::Tensor qs, torch::Tensor scales, torch::Tensor xq,
+                   torch::Tensor xs, torch::Tensor xbs, torch::Tensor y,
+                   int64_t batch) {
+    // y f32 [batch, d] = the Q40 x Q80 product of the first `batch` rows
+    tile_dispatch<GT_PLAIN>(qs, scales, xq, xs, xbs, y, nullptr, batch);
+}
+
+void q40_gemm_tile_resid(torch::Tensor qs, torch::Tensor scales,
+                         torch::Tensor xq, torch::Tensor xs, torch::Tensor xbs,
+                         torch::Tensor x, torch::Tensor ssq, int64_t batch) {
+    // x[b] += product, the rows' squares into ssq's spread slots
+    CHECK_CUDA(ssq); CHECK_CONT(ssq);
+    TORCH_CHECK(ssq.scalar_type() == torch::kFloat32
+                && ssq.numel() >= batch * SSQ_SPREAD * SSQ_PAD,
+                "ssq shorter than `batch` rows of spread slots");
+    tile_dispatch<GT_RESID>(qs, scales, xq, xs, xbs, x, ssq.data_ptr<float>(),
+                            batch);
+}
+
 void register_gemm(py::module &m) {
+    m.def("q40_gemm_tile", &q40_gemm_tile, py::arg("qs"), py::arg("scales"),
+          py::arg("xq"), py::arg("xs"), py::arg("xbs"), py::arg("y"),
+          py::arg("batch"));
+    m.def("q40_gemm_tile_resid", &q40_gemm_tile_resid, py::arg("qs"),
+          py::arg("scales"), py::arg("xq"), py::arg("xs"), py::arg("xbs"),
+          py::arg("x"), py::arg("ssq"), py::arg("batch"));
     m.def("q40_gemm_stream", &q40_gemm_stream, py::arg("qs"), py::arg("scales"),
           py::arg("xq"), py::arg("xs"), py::arg("xbs"), py::arg("y"),
           py::arg("batch"), py::arg("rows") = 0, py::arg("waves") = 0);

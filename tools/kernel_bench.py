@@ -417,6 +417,67 @@ def stream_ab(rounds=3, batches=(8, 16, 32), sweep=False):
         del qs, sc
 
 
+def tile_ab(rounds=3, batches=(64, 96, 128)):
+    """q40_gemm_tile at 64, 96 and 128 rows against the parent's best for the
+    same rows: q40_gemm_stream once per 32 rows (its residual form on wo and
+    w2, which is what replaces q40_gemm + add_ssq there). Weights rotate and
+    candidates interleave as in stream_ab; median us per call and the tile
+    kernel's weight bytes/s against the 6.3 TB/s ceiling.
+
+      python tools/kernel_bench.py tile"""
+    print("\n-- q40_gemm_tile vs ceil(rows / 32) x q40_gemm_stream, isolated "
+          "graph, rotating >300 MB of weights (median us per call) --")
+    for tag, d, n, resid in (("wo", 4096, 4096, True), ("w2", 4096, 14336, True),
+                             ("qkv", 6144, 4096, False), ("w13", 28672, 4096, False),
+                             ("cls", 128256, 4096, False)):
+        nbytes = d * n * 0.5625
+        copies = int(300e6 // nbytes) + 1
+        qs = torch.randint(0, 256, (copies, d, n // 2), dtype=torch.uint8,
+                           device=dev, generator=g)
+        sc = (torch.rand((copies, d, n // 32), device=dev, generator=g)
+              * 0.01).to(torch.float16)
+        xq, xs, xbs = mkx(128, n)
+        y = torch.zeros(128, d, device=dev)
+        xr = torch.zeros(128, d, device=dev)
+        sq = torch.zeros(128, 16 * 32, device=dev)
+        it = [0]
+
+        def stream(B):
+            i = it[0] % copies
+            it[0] += 1
+            for b0 in range(0, B, 32):
+                r = slice(b0, min(b0 + 32, B))
+                acts = (xq[r], xs[r], xbs[r])
+                if resid:
+                    k.q40_gemm_stream_resid(qs[i], sc[i], *acts, xr[r], sq[r],
+                                            r.stop - b0)
+                else:
+                    k.q40_gemm_stream(qs[i], sc[i], *acts, y[r], r.stop - b0)
+
+        def tile(B):
+            i = it[0] % copies
+            it[0] += 1
+            if resid:
+                k.q40_gemm_tile_resid(qs[i], sc[i], xq, xs, xbs, xr, sq, B)
+            else:
+                k.q40_gemm_tile(qs[i], sc[i], xq, xs, xbs, y, B)
+
+        for B in batches:
+            cands = {"stream": lambda: stream(B), "tile": lambda: tile(B)}
+            t = {name: [] for name in cands}
+            for _ in range(rounds):
+                for name, fn in cands.items():
+                    it[0] = 0
+                    t[name].append(bench(fn, n=max(16, copies), reps=3))
+            med = {name: statistics.median(v) for name, v in t.items()}
+            print(f"{tag:4s} {d:6d}x{n:<5d} NB={B:3d}  " + "  ".join(
+                f"{name}: {v:7.2f}" for name, v in med.items())
+                + f"  tile {nbytes / med['tile'] / 1e6:5.2f} TB/s"
+                f" ({100 * nbytes / med['tile'] / 6.3e6:3.0f}% of 6.3)",
+                flush=True)
+        del qs, sc
+
+
 if sys.argv[1:] == ["attn"]:
     attn_ab()
     sys.exit(0)
@@ -466,6 +527,9 @@ def mkx(nb, n):
 
 if sys.argv[1:2] == ["stream"]:
     stream_ab(sweep="--sweep" in sys.argv[2:])
+    sys.exit(0)
+if sys.argv[1:] == ["tile"]:
+    tile_ab()
     sys.exit(0)
 
 NB = 1
