@@ -51,6 +51,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "--max-seq-len rows per slot")
     p.add_argument("--page-size", type=int, default=64,
                    help="rows per KV page (--kv-pages): a power of two, 4..256")
+    p.add_argument("--prefix-attn", type=int, default=0, choices=[0, 1, 2],
+                   help="HIP backend with --kv-pages: decode steps read the "
+                        "leading pages that several slots share once per "
+                        "group of sequences instead of once per sequence. 1 "
+                        "serves an f16 KV cache, 2 a q80 one as well; 0 "
+                        "(default) keeps the per-sequence attention")
     p.add_argument("--kv-dtype", default=None, choices=["f16", "f32", "q80"],
                    help="KV cache format. HIP backend: f16 is the default "
                         "(f32 under DLLAMA_KV_F32=1); q80 stores int8 codes + "
@@ -131,6 +137,11 @@ def load_engine(args):
             raise SystemExit(
                 f"error: --page-size must be a power of two in 4..256 "
                 f"(got {page_size})")
+    prefix_attn = getattr(args, "prefix_attn", 0)
+    if prefix_attn and not kv_pages:
+        raise SystemExit(
+            "error: --prefix-attn needs --kv-pages: only a paged KV cache "
+            "shares prompt prefixes between slots")
     paging = dict(kv_pages=kv_pages, page_size=page_size) if kv_pages else {}
     kv_dtype = getattr(args, "kv_dtype", None)
     if kv_dtype is not None:  # the default passes nothing to the backend
@@ -168,6 +179,8 @@ def load_engine(args):
         # several slots step through forward_rows, which captures its own
         # all-decode graphs lazily: the single-sequence graph is not needed
         model.row_graphs = not args.no_graph
+        if prefix_attn:
+            model.set_prefix_attn(True, q80=prefix_attn == 2)
         if not args.no_graph and slots == 1:
             # RCCL collectives are hipGraph-capturable, so TP decode is one
             # graph replay per token too (every rank captures in lockstep —

@@ -158,6 +158,10 @@ class KVAddr:
         self.chunk = None
         # the GQA-packed MFMA decode attention (set_gqa_attn)
         self.attn_gqa = "attn_gqa" + suffix
+        # the shared-prefix attention (set_prefix_attn): the device tables
+        # (pre_rows, groups, members, n_groups) of a paged row step, staged
+        # with the row table; None = the option does not serve the model
+        self.prefix = None
 
 
 class HipTransformer:
@@ -316,6 +320,23 @@ class HipTransformer:
         # 3072 (18.5 against 18.7); 3584 is the first measured position where
         # the MFMA kernel wins, 19.0 against 28.9 (profiles/r18_gqa_q80.md)
         self.gqa_min_pos_q80 = 3584
+        # shared prefixes read once: on a paged model, row steps above the
+        # wide tier run k_attn_prefix over the leading pages that groups of
+        # decode rows have in common, k_attn_gqa over every row's own suffix
+        # and a combine of both (docs/DESIGN.md §15). Level 1 serves f16
+        # caches, level 2 (prefix_attn_q80) Q80 caches as well, with K and V
+        # entering the MFMA as f16(code * scale). Off by default;
+        # set_prefix_attn on a live model
+        self.prefix_attn = env.get("DLLAMA_ATTN_PREFIX", "0") in ("1", "2")
+        self.prefix_attn_q80 = env.get("DLLAMA_ATTN_PREFIX", "0") == "2"
+        # S_pre = 16 was the fastest of 4..32 at a 3584-token prefix (8 ties
+        # it at 1024). A group qualifies where the path was measured to win:
+        # 32 rows behind 3584 tokens, 6.78 against 7.18 ms per step; 8 rows
+        # there and 32 rows behind 1024 tokens lose, nothing between was
+        # measured (profiles/r20_prefix_attention.md)
+        self.prefix_splits = 16
+        self.prefix_min_tokens = 3584  # a shorter common prefix is not grouped
+        self.prefix_min_rows = 32      # nor one that fewer rows share
         self._gqa_pos_ok = True  # the last _pick_splits: at or above it
         self._gqa_seq_ok = True  # the same of the last single-sequence step
         # the S in force above the wide tier, put back when a step leaves it
@@ -541,6 +562,12 @@ class HipTransformer:
             n = self.prefill_rows * c.n_heads0 * self.attn_splits
             self.wide.attn_ml = torch.zeros(n * 2, device=dev)
             self.wide.attn_o = torch.zeros(n * c.head_dim, device=dev)
+        # the shared-prefix attention's own partials: S_pre per (row, head)
+        self.pre_ml = self.pre_o = None
+        if self._prefix_served():
+            n = self.n_batches * c.n_heads0 * self.prefix_splits
+            self.pre_ml = torch.zeros(n * 2, device=dev)
+            self.pre_o = torch.zeros(n * c.head_dim, device=dev)
 
     def _check_prefill_rows(self):
         """prefill_rows is 0 or a chunk size the wide path serves, on a model
@@ -726,6 +753,15 @@ class HipTransformer:
                 *(self.zq.triple() if emit_q80 else ()),
                 **self._kv_scales(l))
             return
+        if addr.prefix is not None and self._prefix_step():
+            self.k.attn_prefix_paged(
+                self.qkv_out, self.qkv_ld, self.k_cache[l], self.v_cache[l],
+                self.zbuf[:B], *addr.where, *addr.prefix, B, c.n_heads0,
+                self.kv_mul, c.head_dim, self.attn_splits, self.attn_ml,
+                self.attn_o, self.prefix_splits, self.pre_ml, self.pre_o,
+                *(self.zq.triple() if emit_q80 else ()),
+                **self._kv_scales(l))
+            return
         if self._gqa_step():
             getattr(self.k, addr.attn_gqa)(
                 self.qkv_out, self.qkv_ld, self.k_cache[l], self.v_cache[l],
@@ -761,6 +797,37 @@ class HipTransformer:
         self.gqa_attn = bool(on)
         self.gqa_attn_q80 = bool(on) and bool(q80)
         self.graphs.clear()
+
+    def _prefix_served(self) -> bool:
+        """The shared-prefix option is on at a level that serves this model:
+        paged, an f16 cache (or Q80 at the second level), and heads the
+        kernels have instantiations for."""
+        served = self.kv_dtype == "f16" or (
+            self.kv_dtype == "q80" and self.prefix_attn_q80)
+        return bool(self.prefix_attn and served and self.page_map is not None
+                    and self.cfg.head_dim in (64, 128) and self.kv_mul <= 16)
+
+    def _prefix_step(self) -> bool:
+        """A row step the chunk kernel left takes the prefix / suffix /
+        combine launches, whether or not a group qualified: above the wide
+        tier (S > 1) every step does, so a captured row graph stays valid as
+        groups come and go."""
+        return self._prefix_served() and self.attn_splits > 1
+
+    def set_prefix_attn(self, on: bool = True, q80: bool = False):
+        """Row steps of a paged model read shared leading pages once per
+        group of decode rows (or stop doing so); q80=True extends it to a Q80
+        KV cache, which `on` alone leaves on its old launches. Drops the
+        captured graphs, and the row-step staging with the prefix scratch is
+        rebuilt for the new setting."""
+        if on and self.page_map is None:
+            raise ValueError(
+                "the shared-prefix attention needs a paged KV cache (kv_pages)")
+        self.prefix_attn = bool(on)
+        self.prefix_attn_q80 = bool(on) and bool(q80)
+        self.graphs.clear()
+        self._rows_io = None
+        self._alloc_attn_scratch()
 
     def _chunk_step(self, B: int, addr: KVAddr):
         """The chunk attention's extra arguments if this step takes it, else
@@ -1539,28 +1606,66 @@ class HipTransformer:
         on. Built on first use, with its pinned host twin."""
         if self._rows_io is None:
             NB, dev = self.n_batches, self.device
-            self._rows_io = io = torch.zeros(7 * NB, dtype=torch.int64, device=dev)
+            # with the shared-prefix attention on, its tables follow the run
+            # table: pre_rows int32 [NB, 2], groups int32 [NB/2, 2], members
+            # int32 [NB] and the live group count (one word)
+            prefix = self._prefix_served()
+            self._rows_words = words = 9 * NB + 1 if prefix else 7 * NB
+            self._rows_io = io = torch.zeros(words, dtype=torch.int64, device=dev)
             self.row_tokens = io[:NB]
             self.row_params = io[NB:5 * NB].view(torch.float64).view(NB, 4)
             self.rows = io[5 * NB:6 * NB].view(torch.int32).view(NB, 2)
-            self.runs = io[6 * NB:].view(torch.int32).view(NB, 2)
+            self.runs = io[6 * NB:7 * NB].view(torch.int32).view(NB, 2)
             if self.page_map is not None:
                 self.row_addr = KVAddr("_paged", self.rows, self.page_table,
                                        self.page_size)
             else:
                 self.row_addr = KVAddr("_rows", self.rows)
+            self._pre_dev = None  # the prefix tables the device holds
+            if prefix:
+                self.row_addr.prefix = self._prefix_views(io)
             # [token, status] of every row, then (set_logprobs) the rows'
             # f32 [NB, 22] and i32 [NB, 20] blocks: one copy returns it all
             self._rows_out = torch.zeros(NB * LP_WORDS, dtype=torch.int64,
                                          device=dev)
             self.rows_sample_out = self._rows_out[:2 * NB].view(NB, 2)
-            self._rows_host = torch.zeros(7 * NB, dtype=torch.int64)
+            self._rows_host = torch.zeros(words, dtype=torch.int64)
             if dev.type == "cuda":
                 self._rows_host = self._rows_host.pin_memory()
             self._rows_copied = None  # event: the last staging copy is done
             self._rows_dev = []       # the table rows the device holds
             self._row_samplers = []
         return self._rows_io
+
+    def _prefix_views(self, buf):
+        """(pre_rows [NB, 2], groups [NB/2, 2], members [NB], n_groups) as
+        int32 views of a row-step buffer, the device's or its host twin."""
+        NB = self.n_batches
+        w = buf[7 * NB:].view(torch.int32)
+        return (w[:2 * NB].view(NB, 2), w[2 * NB:3 * NB].view(NB // 2, 2),
+                w[3 * NB:4 * NB], w[4 * NB:])
+
+    def _stage_prefix(self, slots, positions):
+        """The step's shared-prefix tables as Python lists (pre_rows, groups,
+        members, count): decode rows (the only row of their slot in the
+        step) grouped by prefix_groups, every other row ungrouped."""
+        from .rows import prefix_groups
+        pm, NB = self.page_map, self.n_batches
+        once = {s for s in slots if slots.count(s) == 1}
+        found = prefix_groups(
+            [pm.table[s] if s in once else None for s in slots], positions,
+            pm.page_size, 128 // self.kv_mul, self.prefix_min_rows,
+            self.prefix_min_tokens)[:NB // 2]
+        pre = [[-1, 0] for _ in range(NB)]
+        groups = [[0, 0] for _ in range(NB // 2)]
+        members = []
+        for g, (rows, plen) in enumerate(found):
+            groups[g] = [len(members), len(rows)]
+            members += rows
+            for b in rows:
+                pre[b] = [g, plen]
+        members += [0] * (NB - len(members))
+        return pre, groups, members, len(found)
 
     def _row_sampler(self, b: int) -> DeviceSampler:
         """Row b's sampler: its parameters and result live in row b of
@@ -1608,8 +1713,16 @@ class HipTransformer:
             runs = row_runs(slots)
             if max(n for _, n in runs) < self.chunk_min_rows:
                 runs = None
+        # the shared-prefix tables travel behind both, and only when they
+        # differ from what the device holds: never in steady decode
+        pre = None
+        if self.row_addr.prefix is not None:
+            pre = self._stage_prefix(slots, positions)
+            if pre == self._pre_dev:
+                pre = None
         words = 5 * NB
-        if runs is not None or self._rows_dev[:B] != table:
+        if (runs is not None or pre is not None
+                or self._rows_dev[:B] != table):
             ht = host[5 * NB:6 * NB].view(torch.int32).view(NB, 2)
             ht.zero_()
             ht[:B] = torch.tensor(table, dtype=torch.int32)
@@ -1617,11 +1730,17 @@ class HipTransformer:
             self._rows_dev = list(table)
         self.row_addr.chunk = None
         if runs is not None:  # the run table travels behind the row table
-            hr = host[6 * NB:].view(torch.int32).view(NB, 2)
+            hr = host[6 * NB:7 * NB].view(torch.int32).view(NB, 2)
             hr.zero_()
             hr[:len(runs)] = torch.tensor(runs, dtype=torch.int32)
             words = 7 * NB
             self.row_addr.chunk = (self.runs, len(runs))
+        if pre is not None:
+            for view, vals in zip(self._prefix_views(host), pre[:3]):
+                view.copy_(torch.tensor(vals, dtype=torch.int32).view_as(view))
+            self._prefix_views(host)[3][0] = pre[3]
+            words = self._rows_words
+            self._pre_dev = pre
         self._rows_io[:words].copy_(host[:words], non_blocking=True)
         if self.device.type == "cuda":
             self._rows_copied = torch.cuda.Event()

@@ -151,6 +151,45 @@ def row_runs(slots: list[int]) -> list[tuple[int, int]]:
     return runs
 
 
+def prefix_groups(page_rows, positions: list[int], page_size: int,
+                  cols_per_group: int, min_rows: int = 2,
+                  min_tokens: int = 0) -> list[tuple[list[int], int]]:
+    """The shared-prefix groups of a step as (member batch rows, plen):
+    decode rows whose sequences start with the same run of pool pages, which
+    the prefix attention reads once per group. page_rows[b] is row b's
+    page-id list (PageMap.table of its slot), or None for a row that is no
+    decode row and joins no group.
+
+    Rows are bucketed by their first page id; a bucket's prefix is the
+    longest common run of leading ids, over entries mapped (>= 0) in every
+    member. A bucket with at least min_rows members and plen = pages *
+    page_size >= min_tokens qualifies, and is cut in row order into groups
+    of at most cols_per_group members; min_rows counts the bucket, not its
+    cuts. Groups come in the order of their first rows."""
+    buckets: dict[int, list[int]] = {}
+    for b, pages in enumerate(page_rows):
+        if pages is not None and len(pages) and pages[0] >= 0:
+            buckets.setdefault(pages[0], []).append(b)
+    out = []
+    for rows in buckets.values():  # insertion order: by first row
+        if len(rows) < max(min_rows, 1):
+            continue
+        lists = [page_rows[b] for b in rows]
+        n = 0
+        while (n < min(len(p) for p in lists) and lists[0][n] >= 0
+               and all(p[n] == lists[0][n] for p in lists)):
+            n += 1
+        plen = n * page_size
+        if plen < max(min_tokens, 1):
+            continue
+        # a page two slots name is full and read-only (PageMap.check): the
+        # prefix lies wholly below every member's position
+        assert all(positions[b] >= plen for b in rows), (rows, plen)
+        for i in range(0, len(rows), cols_per_group):
+            out.append((rows[i: i + cols_per_group], plen))
+    return out
+
+
 def is_decode_step(slots: list[int]) -> bool:
     """Every row belongs to another sequence: one decode row each."""
     return len(set(slots)) == len(slots)

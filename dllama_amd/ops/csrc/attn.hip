@@ -1502,6 +1502,384 @@ k_attn_gqa(const float *__restrict__ q, int q_ld,
     }
 }
 
+// ------------------------------------------------- shared-prefix attention
+// The producer of the split scratch for what several sequences have in
+// common: decode rows whose sequences start with the same run of pool pages
+// (a system prompt mapped into many slots) attend that run once per group
+// instead of once per row. The host groups the rows (models/rows.py
+// prefix_groups) and stages three tables: pre_rows int32 [B, 2] = {group or
+// -1, plen} per batch row, groups int32 [G, 2] = {first, count} into members
+// int32 [..] (batch-row indices), and the live group count on the device.
+//
+// Grid (n_kv_heads0, G, S_pre), 4 waves; nothing in it depends on the
+// grouping or on positions, a workgroup at or past the live group count
+// leaves on a uniform branch, so a captured step replays for any grouping.
+// Column c of a workgroup is (member c / kv_mul, query head c % kv_mul of the
+// KV head): up to 128 columns, wave w owns columns 32w .. 32w+31 as the N
+// dimension of v_mfma_f32_32x32x16_f16. Split sp walks the 32-timestep tiles
+// sp, sp + S_pre, .. below plen. Every K/V tile is staged in LDS once per
+// workgroup (k_attn_chunk's tiles: K [t][d], V transposed [d][t], two
+// buffers, one barrier per tile) and read by all four waves: a K/V byte
+// leaves the cache once per 128 columns, which is why this kernel stages
+// through LDS and not through registers as k_attn_gqa does. Page ids come
+// from the first member's list, one tile ahead of the loads.
+//
+// No causal mask: every column sees the whole prefix. Only the tile that
+// holds plen masks, uniformly (t >= plen; possible with pages below 32 rows
+// only), its weights 0 by name. Math, layouts and rounding points are
+// k_attn_chunk's (S^T = K Q^T, lane-local online softmax, registers 8c..8c+7
+// of the scores as the B operand of O^T += V^T P^T).
+//
+// The tables are the host's, but no table can send a load or store astray:
+// the group is clamped to the member list, members to the batch, plen to the
+// smallest member position (a shared page is full and read-only, so a valid
+// plen lies at or below it), and K/V are only ever found through the first
+// member's page list below that plen.
+//
+// The rest of a row's history is the suffix: k_attn_gqa over SuffixRows,
+// which moves the row's time origin to plen (K was roped before it was
+// cached, so nothing else changes), filling the ordinary split scratch.
+// k_attn_combine_pre merges both sets of partials: the split of a softmax at
+// plen is the same exact (m, l, o) algebra as the split across S.
+struct SuffixRows : PagedRows {
+    const int *pre;  // pre_rows: int32 [B, 2] = {group or -1, plen}
+    __device__ int plen(int b) const {
+        return min(max(pre[2 * b + 1], 0), rows[2 * b + 1]);
+    }
+    __device__ int position(int b) const { return rows[2 * b + 1] - plen(b); }
+    __device__ const int *seq_pages(int b) const {
+        return pages + rows[2 * b] + (plen(b) >> shift);
+    }
+    __device__ int64_t cache_row(int b, int t) const {
+        return ((int64_t)seq_pages(b)[t >> shift] << shift)
+             + (t & ((1 << shift) - 1));
+    }
+};
+
+constexpr int PRE_T = 32;      // timesteps per tile = MFMA M of the scores
+constexpr int PRE_NW = 4;      // waves per workgroup
+constexpr int PRE_COLS = 128;  // (member, head) columns per workgroup
+constexpr int PRE_HEADS = 16;  // kv_mul served
+
+template <int VEC, typename KVT, typename ROWS>
+__global__ void __launch_bounds__(PRE_NW * WAVE, 2)
+k_attn_prefix(const float *__restrict__ q, int q_ld,
+              const KVT *__restrict__ kc_all, const KVT *__restrict__ vc_all,
+              const ROWS rows, const int *__restrict__ pre_rows,
+              const int *__restrict__ groups, const int *__restrict__ members,
+              int n_members, const int *__restrict__ n_groups, int batch,
+              int n_heads0, int kv_mul, int kv_dim0, float scale,
+              float *__restrict__ ml_scratch, float *__restrict__ o_scratch) {
+    constexpr bool Q8 = kKVQ80<KVT>;
+    static_assert(ROWS::kPaged, "a shared prefix is a run of pool pages");
+    constexpr int hd = VEC * WAVE;
+    constexpr int KLD = hd + 8;     // halves per K row: 16-byte rows, 4-bank skew
+    constexpr int VLD = PRE_T + 4;  // halves per V^T row (one d): 8-byte rows
+    constexpr int DCH = hd / 8;     // 16-byte chunks per cache row of the head
+    constexpr int NLD = PRE_T * DCH / (PRE_NW * WAVE);  // chunks per thread
+    static_assert(NLD * PRE_NW * WAVE == PRE_T * DCH, "tile / threads");
+    __shared__ __attribute__((aligned(16))) _Float16 sk[2][PRE_T * KLD];
+    __shared__ __attribute__((aligned(16))) _Float16 sv[2][hd * VLD];
+    __shared__ int smin[PRE_NW];
+
+    const int grp = blockIdx.y;
+    if (grp >= n_groups[0]) return;  // uniform: no such group in this step
+    const int kvh = blockIdx.x;
+    const int sp = blockIdx.z;
+    const int S = gridDim.z;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+    const int lane = threadIdx.x % WAVE;
+    const int row = lane & 31;  // column of the wave (B / C operand column)
+    const int hi = lane >> 5;
+
+    // the group, clamped to the member list and to the columns there are
+    const int first = min(max(groups[2 * grp], 0), n_members - 1);
+    const int count = min(min(groups[2 * grp + 1], n_members - first),
+                          PRE_COLS / kv_mul);
+    if (count < 1) return;  // uniform
+    const int ncols = count * kv_mul;
+    auto member = [&](int i) {
+        return min(max(members[first + i], 0), batch - 1);
+    };
+    const int b0 = __builtin_amdgcn_readfirstlane(member(0));
+
+    // plen: the first member's, at most the smallest position of the group
+    int mp = (int)threadIdx.x < count ? rows.position(member(threadIdx.x))
+                                      : 0x7fffffff;
+    #pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        mp = min(mp, __shfl_xor(mp, off, WAVE));
+    if (lane == 0) smin[wave] = mp;
+    __syncthreads();
+    const int plen = __builtin_amdgcn_readfirstlane(
+        min(max(pre_rows[2 * b0 + 1], 0),
+            min(min(smin[0], smin[1]), min(smin[2], smin[3]))));
+
+    // this lane's column
+    const int col = 32 * wave + row;
+    const bool real = col < ncols;        // else padding: q = 0, never written
+    const bool active = 32 * wave < ncols;  // wave-uniform
+    const int b = member(real ? col / kv_mul : 0);
+    const int h0 = kvh * kv_mul + (real ? col % kv_mul : 0);
+
+    const KVT *kc = kc_all + kvh * hd;
+    const KVT *vc = vc_all + kvh * hd;
+    // Q80: the scale planes, f16 [rows, kv_dim0/32], from the same cache row
+    [[maybe_unused]] const int nblk = kv_dim0 / QB;
+    [[maybe_unused]] const _Float16 *ks = nullptr, *vs = nullptr;
+    if constexpr (Q8) {
+        ks = reinterpret_cast<const _Float16 *>(rows.ks) + kvh * (hd / QB);
+        vs = reinterpret_cast<const _Float16 *>(rows.vs) + kvh * (hd / QB);
+    }
+
+    // staging, as k_attn_chunk: a thread holds NLD 8-element chunks of the K
+    // tile and of the V tile between their global load and their LDS store,
+    // 16 bytes of f16 or 8 codes and their block's scale. A timestep at or
+    // past plen (last tile only) re-reads row plen-1: valid, masked below.
+    // With pages of 32 rows or more a tile lies in one page: one uniform id.
+    using Staged = std::conditional_t<Q8, int2, v8h_t>;
+    Staged kreg[NLD], vreg[NLD];
+    [[maybe_unused]] _Float16 kscl[NLD], vscl[NLD];
+    int pgid[NLD];  // page of each chunk of the next tile_load
+    const int pshift = rows.shift;
+    const int *seqp =
+        rows.pages + __builtin_amdgcn_readfirstlane(rows.rows[2 * b0]);
+    auto page_fetch = [&](int tile) {
+        if (tile * PRE_T >= plen) return;  // no such tile
+        if (pshift >= 5) {
+            const int id = seqp[(tile * PRE_T) >> pshift];
+            #pragma unroll
+            for (int it = 0; it < NLD; it++) pgid[it] = id;
+        } else {
+            #pragma unroll
+            for (int it = 0; it < NLD; it++) {
+                const int idx = threadIdx.x + it * PRE_NW * WAVE;
+                const int t = min(tile * PRE_T + idx / DCH, plen - 1);
+                pgid[it] = seqp[t >> pshift];
+            }
+        }
+    };
+    auto tile_load = [&](int tile) {
+        #pragma unroll
+        for (int it = 0; it < NLD; it++) {
+            const int idx = threadIdx.x + it * PRE_NW * WAVE;
+            const int t = min(tile * PRE_T + idx / DCH, plen - 1);
+            const int64_t r = ((int64_t)pgid[it] << pshift)
+                            + (t & ((1 << pshift) - 1));
+            const int64_t off = r * kv_dim0 + (idx % DCH) * 8;
+            kreg[it] = *reinterpret_cast<const Staged *>(kc + off);
+            vreg[it] = *reinterpret_cast<const Staged *>(vc + off);
+            if constexpr (Q8) {
+                const int64_t so = r * nblk + (idx % DCH) * 8 / QB;
+                kscl[it] = ks[so];
+                vscl[it] = vs[so];
+            }
+        }
+    };
+    auto tile_store = [&](int buf) {
+        #pragma unroll
+        for (int it = 0; it < NLD; it++) {
+            const int idx = threadIdx.x + it * PRE_NW * WAVE;
+            const int t = idx / DCH, d = (idx % DCH) * 8;
+            v8h_t kh, vh;
+            if constexpr (Q8) {
+                kh = q80_codes_f16(kreg[it], kscl[it]);
+                vh = q80_codes_f16(vreg[it], vscl[it]);
+            } else {
+                kh = kreg[it];
+                vh = vreg[it];
+            }
+            *reinterpret_cast<v8h_t *>(&sk[buf][t * KLD + d]) = kh;
+            #pragma unroll
+            for (int i = 0; i < 8; i++) sv[buf][(d + i) * VLD + t] = vh[i];
+        }
+    };
+
+    // q * scale in f32, rounded to f16 once: the B operand of the scores
+    v8h_t qf[hd / 16];
+    #pragma unroll
+    for (int kb = 0; kb < hd / 16; kb++) {
+        float4 x0 = {0.f, 0.f, 0.f, 0.f}, x1 = x0;
+        if (real) {
+            const float *qp = q + (int64_t)b * q_ld + h0 * hd + kb * 16 + hi * 8;
+            x0 = *reinterpret_cast<const float4 *>(qp);
+            x1 = *reinterpret_cast<const float4 *>(qp + 4);
+        }
+        qf[kb] = v8h_t{
+            (_Float16)mul_f32(x0.x, scale), (_Float16)mul_f32(x0.y, scale),
+            (_Float16)mul_f32(x0.z, scale), (_Float16)mul_f32(x0.w, scale),
+            (_Float16)mul_f32(x1.x, scale), (_Float16)mul_f32(x1.y, scale),
+            (_Float16)mul_f32(x1.z, scale), (_Float16)mul_f32(x1.w, scale)};
+    }
+
+    v16f_t o[hd / 32];
+    #pragma unroll
+    for (int mb = 0; mb < hd / 32; mb++)
+        #pragma unroll
+        for (int r = 0; r < 16; r++) o[mb][r] = 0.0f;
+    // this lane's half of the column's l (its 16 timesteps per tile); m is
+    // the column's, equal in lane and lane^32
+    float m = -1e30f, l = 0.0f;
+
+    // double-buffered: tile i+S is in flight from the cache while tile i is
+    // multiplied; one barrier per tile (the buffer stored to at the end of an
+    // iteration was last read before the previous barrier)
+    int tile = sp, buf = 0;
+    page_fetch(tile);
+    if (tile * PRE_T < plen) {
+        tile_load(tile);
+        page_fetch(tile + S);
+        tile_store(0);
+    }
+    __syncthreads();
+    for (; tile * PRE_T < plen; tile += S, buf ^= 1) {
+        const bool more = (tile + S) * PRE_T < plen;
+        if (more) {
+            tile_load(tile + S);
+            page_fetch(tile + 2 * S);
+        }
+        if (active) {
+            const int t0 = tile * PRE_T;
+            v16f_t s;
+            #pragma unroll
+            for (int r = 0; r < 16; r++) s[r] = 0.0f;
+            #pragma unroll
+            for (int kb = 0; kb < hd / 16; kb++) {
+                const v8h_t kf = *reinterpret_cast<const v8h_t *>(
+                    &sk[buf][row * KLD + kb * 16 + hi * 8]);
+                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kb], s,
+                                                           0, 0, 0);
+            }
+            // only the tile that holds plen masks, for every column alike
+            const bool edge = t0 + PRE_T > plen;
+            float mx = -1e30f;
+            #pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int t = t0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                if (edge && t >= plen) s[r] = -1e30f;
+                mx = fmaxf(mx, s[r]);
+            }
+            mx = fmaxf(mx, __shfl_xor(mx, 32, WAVE));
+            // the tile's first timestep is below plen: mx is a real score
+            const float mn = fmaxf(m, mx);
+            constexpr float LOG2E = 1.4426950408889634f;
+            const float nmn = -mn * LOG2E;
+            // m = -1e30 (the first tile): l and o are 0, any finite f does
+            const float f = m > -1e30f
+                ? __builtin_amdgcn_exp2f(fma_f32(m, LOG2E, nmn)) : 0.0f;
+            float p[16], ls = 0.0f;
+            #pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int t = t0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                // a masked weight is 0 by name, not left to exp
+                p[r] = (edge && t >= plen) ? 0.0f
+                    : __builtin_amdgcn_exp2f(fma_f32(s[r], LOG2E, nmn));
+                ls += p[r];
+            }
+            l = fma_f32(l, f, ls);
+            m = mn;
+            v8h_t pf[2];
+            #pragma unroll
+            for (int c = 0; c < 2; c++)
+                #pragma unroll
+                for (int j = 0; j < 8; j++) pf[c][j] = (_Float16)p[8 * c + j];
+            #pragma unroll
+            for (int mb = 0; mb < hd / 32; mb++) {
+                #pragma unroll
+                for (int r = 0; r < 16; r++) o[mb][r] = mul_f32(o[mb][r], f);
+                #pragma unroll
+                for (int c = 0; c < 2; c++) {
+                    const _Float16 *vp =
+                        &sv[buf][(mb * 32 + row) * VLD + 16 * c + 4 * hi];
+                    const v4h_t v0 = *reinterpret_cast<const v4h_t *>(vp);
+                    const v4h_t v1 = *reinterpret_cast<const v4h_t *>(vp + 8);
+                    const v8h_t vf = __builtin_shufflevector(
+                        v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
+                    o[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(
+                        vf, pf[c], o[mb], 0, 0, 0);
+                }
+            }
+        }
+        if (more) tile_store(buf ^ 1);
+        __syncthreads();
+    }
+
+    if (active) {
+        l += __shfl_xor(l, 32, WAVE);
+        if (real) {
+            // a split with no tile leaves m = -1e30, l = 0, o = 0
+            const int64_t slot = ((int64_t)b * n_heads0 + h0) * S + sp;
+            if (hi == 0) {
+                ml_scratch[slot * 2] = m;
+                ml_scratch[slot * 2 + 1] = l;
+            }
+            #pragma unroll
+            for (int mb = 0; mb < hd / 32; mb++)
+                #pragma unroll
+                for (int g = 0; g < 4; g++)
+                    *reinterpret_cast<float4 *>(
+                        o_scratch + slot * hd + mb * 32 + 8 * g + 4 * hi) =
+                        float4{o[mb][4 * g], o[mb][4 * g + 1],
+                               o[mb][4 * g + 2], o[mb][4 * g + 3]};
+        }
+    }
+}
+
+// Stage 2 of the shared-prefix attention: k_attn_combine over the S suffix
+// partials of (b, h) and then, for a row with a prefix (plen > 0), its S_pre
+// prefix partials, in that fixed order. An ungrouped row's prefix scratch is
+// never read, so nothing has to be neutral-filled for it.
+template <int VEC, bool QUANT>
+__global__ void k_attn_combine_pre(const float *__restrict__ ml_scratch,
+                                   const float *__restrict__ o_scratch,
+                                   const float *__restrict__ pre_ml,
+                                   const float *__restrict__ pre_o,
+                                   const int *__restrict__ pre_rows,
+                                   float *__restrict__ y,
+                                   int8_t *__restrict__ zq,
+                                   float *__restrict__ zs,
+                                   float *__restrict__ zbs,
+                                   int n_heads0, int S, int S_pre) {
+    const int h0 = blockIdx.x;
+    const int b = blockIdx.y;
+    const int hd = VEC * WAVE;  // blockDim.x == hd
+    const int64_t base = ((int64_t)b * n_heads0 + h0) * S;
+    const int64_t pbase = ((int64_t)b * n_heads0 + h0) * S_pre;
+    const int P = pre_rows[2 * b + 1] > 0 ? S_pre : 0;  // block-uniform
+    float M = -1e30f;
+    for (int sp = 0; sp < S; sp++)
+        M = fmaxf(M, ml_scratch[(base + sp) * 2]);
+    for (int sp = 0; sp < P; sp++)
+        M = fmaxf(M, pre_ml[(pbase + sp) * 2]);
+    float L = 0.0f;
+    for (int sp = 0; sp < S; sp++)
+        L += ml_scratch[(base + sp) * 2 + 1] * __expf(ml_scratch[(base + sp) * 2] - M);
+    for (int sp = 0; sp < P; sp++)
+        L += pre_ml[(pbase + sp) * 2 + 1] * __expf(pre_ml[(pbase + sp) * 2] - M);
+    const float invL = 1.0f / L;
+    const int i = threadIdx.x;
+    float acc = 0.0f;
+    for (int sp = 0; sp < S; sp++)
+        acc += o_scratch[(base + sp) * hd + i]
+             * __expf(ml_scratch[(base + sp) * 2] - M);
+    for (int sp = 0; sp < P; sp++)
+        acc += pre_o[(pbase + sp) * hd + i]
+             * __expf(pre_ml[(pbase + sp) * 2] - M);
+    const float v = acc * invL;
+    if (!QUANT) {
+        y[((int64_t)b * n_heads0 + h0) * hd + i] = v;
+    } else {
+        const Q80Lane c = q80_quant_group32(v);
+        zq[((int64_t)b * n_heads0 + h0) * hd + i] = (int8_t)c.qf;
+        const float bsum = group32_reduce_sum(c.qf);
+        if ((i & 31) == 0) {
+            const int blk = (h0 * hd + i) / QB;
+            zs[(int64_t)b * (n_heads0 * hd / QB) + blk] = c.d;
+            zbs[(int64_t)b * (n_heads0 * hd / QB) + blk] = bsum;
+        }
+    }
+}
+
 // ------------------------------------------------------------------ rope
 // style 0 = llama interleaved pairs (reference ropeLlama_F32,
 // nn-cpu-ops.cpp:843-863), style 1 = falcon/neox half-rotated
@@ -2369,6 +2747,144 @@ void attn_gqa_paged(torch::Tensor q, int64_t q_ld, torch::Tensor kc,
                     zq, zs, zbs, k_scales, v_scales);
 }
 
+// Decode-row attention over a paged cache whose rows share leading pages:
+// k_attn_prefix attends every group's common prefix once into the prefix
+// scratch (pre_ml / pre_o, S_pre partials per (row, head)), k_attn_gqa over
+// SuffixRows attends every row's own rest into the split scratch, and
+// k_attn_combine_pre merges the two. The three launches do not depend on the
+// tables' contents (models/rows.py prefix_groups builds them; the kernels
+// clamp what they read from them): with no live group the first leaves at
+// once and the suffix is the whole history.
+void attn_prefix_paged(torch::Tensor q, int64_t q_ld, torch::Tensor kc,
+                       torch::Tensor vc, torch::Tensor y, torch::Tensor rows,
+                       torch::Tensor page_table, int64_t page_size,
+                       torch::Tensor pre_rows, torch::Tensor groups,
+                       torch::Tensor members, torch::Tensor n_groups_dev,
+                       int64_t batch, int64_t n_heads0, int64_t kv_mul,
+                       int64_t head_dim, int64_t splits,
+                       torch::Tensor ml_scratch, torch::Tensor o_scratch,
+                       int64_t pre_splits, torch::Tensor pre_ml,
+                       torch::Tensor pre_o, OptTensor zq = c10::nullopt,
+                       OptTensor zs = c10::nullopt,
+                       OptTensor zbs = c10::nullopt,
+                       OptTensor k_scales = c10::nullopt,
+                       OptTensor v_scales = c10::nullopt) {
+    const char *name = "attn_prefix_paged";
+    CHECK_CUDA(q);
+    TORCH_CHECK(q.scalar_type() == at::kFloat, name, ": q must be float32");
+    TORCH_CHECK(kc.dim() == 2, name, ": caches are [rows, kv_dim0]");
+    const bool f16 = kc.scalar_type() == at::kHalf
+                  && vc.scalar_type() == at::kHalf;
+    const bool q80 = kc.scalar_type() == at::kChar
+                  && vc.scalar_type() == at::kChar;
+    TORCH_CHECK(f16 || q80, name, " serves a float16 or an int8 (Q80) KV "
+                "cache: use attn_paged for a float32 cache");
+    TORCH_CHECK(q80 || (!k_scales.has_value() && !v_scales.has_value()), name,
+                " takes k_scales / v_scales with an int8 (Q80) KV cache only");
+    TORCH_CHECK(f16 || (k_scales.has_value() && v_scales.has_value()), name,
+                ": an int8 (Q80) KV cache needs k_scales= and v_scales=");
+    const KVScales sc = kv_scales(kc, vc, k_scales, v_scales);
+    TORCH_CHECK(head_dim == 64 || head_dim == 128, name,
+                " serves head_dim 64 and 128 (got ", head_dim,
+                "): use attn_paged");
+    TORCH_CHECK(kv_mul >= 1 && kv_mul <= PRE_HEADS, name, " serves kv_mul 1..",
+                PRE_HEADS, " (got ", kv_mul, "): use attn_paged");
+    TORCH_CHECK(n_heads0 % kv_mul == 0, name, ": n_heads0 (", n_heads0,
+                ") must be a multiple of kv_mul (", kv_mul, ")");
+    TORCH_CHECK(splits <= 65535 && pre_splits <= 65535 && batch <= 65535, name,
+                ": batch, splits and pre_splits are grid dimensions, at most "
+                "65535 each");
+    TORCH_CHECK(batch >= 1 && splits >= 1 && pre_splits >= 1 && q_ld % 4 == 0
+                && kc.is_contiguous() && vc.is_contiguous()
+                && kc.sizes() == vc.sizes()
+                && kc.size(1) == n_heads0 / kv_mul * head_dim,
+                name, ": contiguous caches [rows, n_kv_heads0 * head_dim], "
+                "q_ld a multiple of 4");
+    const PagedRows paged = paged_rows(rows, page_table, page_size, batch, kc);
+    auto int_table = [&](const torch::Tensor &t, const char *what) {
+        CHECK_CUDA(t);
+        TORCH_CHECK(t.scalar_type() == at::kInt && t.is_contiguous()
+                    && t.device() == kc.device(), name, ": ", what,
+                    " must be a contiguous int32 tensor on the cache's device");
+    };
+    int_table(pre_rows, "pre_rows");
+    int_table(groups, "groups");
+    int_table(members, "members");
+    int_table(n_groups_dev, "n_groups_dev");
+    TORCH_CHECK(pre_rows.dim() == 2 && pre_rows.size(1) == 2
+                && pre_rows.size(0) >= batch, name,
+                ": pre_rows must be int32 [>= batch, 2]");
+    TORCH_CHECK(groups.dim() == 2 && groups.size(1) == 2
+                && groups.size(0) >= 1 && groups.size(0) <= 65535, name,
+                ": groups must be int32 [1..65535, 2]");
+    TORCH_CHECK(members.numel() >= 1 && n_groups_dev.numel() >= 1, name,
+                ": members and n_groups_dev must not be empty");
+    const int64_t slots = batch * n_heads0 * splits;
+    TORCH_CHECK(ml_scratch.numel() >= slots * 2
+                && o_scratch.numel() >= slots * head_dim,
+                name, ": split scratch too small for ", slots, " partials");
+    const int64_t pslots = batch * n_heads0 * pre_splits;
+    TORCH_CHECK(pre_ml.numel() >= pslots * 2
+                && pre_o.numel() >= pslots * head_dim,
+                name, ": prefix scratch too small for ", pslots, " partials");
+    for (const torch::Tensor *t : {&ml_scratch, &o_scratch, &pre_ml, &pre_o})
+        TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous()
+                    && t->device() == kc.device(), name,
+                    ": scratch must be contiguous float32 on the cache's device");
+    const bool quant = zq.has_value();
+    float *yp = quant ? nullptr : y.data_ptr<float>();
+    int8_t *zqp = quant ? zq->data_ptr<int8_t>() : nullptr;
+    float *zsp = quant ? zs->data_ptr<float>() : nullptr;
+    float *zbsp = quant ? zbs->data_ptr<float>() : nullptr;
+    const int kv_dim0 = kc.size(1);
+    const float scale = 1.0f / sqrtf((float)head_dim);
+    const int n_kv = n_heads0 / kv_mul;
+    const SuffixRows suffix{paged, pre_rows.data_ptr<int>()};
+    with_head_vec(head_dim, [&](auto vec_const) {
+        constexpr int V = decltype(vec_const)::value;
+        with_kv_ptrs(kc, vc, [&](auto *kcp, auto *vcp) {
+            using KVT = std::remove_pointer_t<decltype(kcp)>;
+            auto launch = [&](auto prows, auto srows) {
+                hipLaunchKernelGGL((k_attn_prefix<V, KVT, decltype(prows)>),
+                                   dim3(n_kv, groups.size(0), pre_splits),
+                                   dim3(PRE_NW * WAVE), 0, cur_stream(),
+                                   q.data_ptr<float>(), (int)q_ld, kcp, vcp,
+                                   prows, pre_rows.data_ptr<int>(),
+                                   groups.data_ptr<int>(),
+                                   members.data_ptr<int>(),
+                                   (int)members.numel(),
+                                   n_groups_dev.data_ptr<int>(), (int)batch,
+                                   (int)n_heads0, (int)kv_mul, kv_dim0, scale,
+                                   pre_ml.data_ptr<float>(),
+                                   pre_o.data_ptr<float>());
+                hipLaunchKernelGGL((k_attn_gqa<V, KVT, decltype(srows)>),
+                                   dim3(n_kv, batch, splits),
+                                   dim3(GQA_NW * WAVE), 0, cur_stream(),
+                                   q.data_ptr<float>(), (int)q_ld, kcp, vcp,
+                                   srows, (int)n_heads0, (int)kv_mul, kv_dim0,
+                                   scale, ml_scratch.data_ptr<float>(),
+                                   o_scratch.data_ptr<float>());
+            };
+            if constexpr (kKVQ80<KVT>)
+                launch(Q80Rows<PagedRows>{paged, sc.k, sc.v},
+                       Q80Rows<SuffixRows>{suffix, sc.k, sc.v});
+            else if constexpr (std::is_same_v<KVT, __half>)
+                launch(paged, suffix);
+        });
+        auto combine = [&](auto quant_const) {
+            hipLaunchKernelGGL(
+                (k_attn_combine_pre<V, decltype(quant_const)::value>),
+                dim3(n_heads0, batch), dim3(V * WAVE), 0, cur_stream(),
+                ml_scratch.data_ptr<float>(), o_scratch.data_ptr<float>(),
+                pre_ml.data_ptr<float>(), pre_o.data_ptr<float>(),
+                pre_rows.data_ptr<int>(), yp, zqp, zsp, zbsp, (int)n_heads0,
+                (int)splits, (int)pre_splits);
+        };
+        if (zqp) combine(std::true_type{});
+        else combine(std::false_type{});
+    });
+}
+
 // The Q80 write kernel for either launcher below; mode as k_rope_kv_q80's
 // MODE (0/1 = the rope style, 2 = q/k-norm + neox).
 template <typename ROWS>
@@ -2623,6 +3139,16 @@ void register_attn(py::module &m) {
           py::arg("splits"), py::arg("ml_scratch"), py::arg("o_scratch"),
           py::arg("zq") = py::none(), py::arg("zs") = py::none(),
           py::arg("zbs") = py::none(), KV_SCALE_ARGS);
+    m.def("attn_prefix_paged", &attn_prefix_paged, py::arg("q"),
+          py::arg("q_ld"), py::arg("kc"), py::arg("vc"), py::arg("y"),
+          py::arg("rows"), py::arg("page_table"), py::arg("page_size"),
+          py::arg("pre_rows"), py::arg("groups"), py::arg("members"),
+          py::arg("n_groups_dev"), py::arg("batch"), py::arg("n_heads0"),
+          py::arg("kv_mul"), py::arg("head_dim"), py::arg("splits"),
+          py::arg("ml_scratch"), py::arg("o_scratch"), py::arg("pre_splits"),
+          py::arg("pre_ml"), py::arg("pre_o"), py::arg("zq") = py::none(),
+          py::arg("zs") = py::none(), py::arg("zbs") = py::none(),
+          KV_SCALE_ARGS);
     m.def("kv_append", &kv_append);
     m.def("attn", &attn, py::arg("q"), py::arg("q_ld"), py::arg("kc"), py::arg("vc"),
           py::arg("y"), py::arg("pos"), py::arg("batch"), py::arg("n_heads0"),

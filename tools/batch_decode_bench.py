@@ -23,6 +23,15 @@ alternately, three times each, per B). --logprobs turns set_logprobs on:
 every step also computes the rows' token log-probabilities (top 20) in the
 graph and copies them back with the tokens.
 
+--shared-prefix N (with --kv-pages; a multiple of --page-size) maps the same
+N / page-size pool pages as the first N positions of every slot: B sequences
+behind one prompt. The shared pages hold zeros, every sequence's own prompt
+follows them in pages of its own, and the timed decode starts at N +
+--prefill (or --context, if that is further). --prefix-attn on|ab runs the
+row steps with set_prefix_attn (ab: off and on alternately, three times
+each, per B, on the one model). DLLAMA_ATTN_GQA=1 in the environment gives
+the off side the GQA-packed attention.
+
 Warmup and timing follow bench.py: untimed warmup steps on the shapes of
 the timed window, then a host clock around `--steps` steps ending in a
 device synchronise. Prints one JSON line.
@@ -66,8 +75,20 @@ def main():
     ap.add_argument("--stream-gemm", default="off", choices=["off", "on", "ab"],
                     help="set_stream_gemm: off, on, or ab = every B timed "
                          "off and on alternately, three times each")
+    ap.add_argument("--shared-prefix", type=int, default=0,
+                    help="positions that every slot maps to the same pages")
+    ap.add_argument("--prefix-attn", default="off", choices=["off", "on", "ab"],
+                    help="set_prefix_attn: off, on, or ab = every B timed off "
+                         "and on alternately, three times each")
     args = ap.parse_args()
-    context = max(args.context, args.prefill)
+    shared = args.shared_prefix
+    if shared and (not args.kv_pages or shared % args.page_size):
+        sys.exit("error: --shared-prefix needs --kv-pages and whole pages")
+    if args.prefix_attn != "off" and not args.kv_pages:
+        sys.exit("error: --prefix-attn needs --kv-pages")
+    if "ab" == args.prefix_attn == args.stream_gemm:
+        sys.exit("error: one ab at a time")
+    context = max(args.context, shared + args.prefill)
     if not torch.cuda.is_available():
         sys.exit("error: batch_decode_bench needs a GPU")  # no CPU fall-back
 
@@ -97,10 +118,12 @@ def main():
     last = context + args.warmup + args.steps
     if last > cfg.seq_len:
         sys.exit("error: context + warmup + steps exceed --seq-len")
-    pages_per_slot = -(-last // args.page_size)
-    if args.kv_pages and pages_per_slot * max(batches) > args.kv_pages:
+    n_shared = shared // args.page_size
+    pages_per_slot = -(-last // args.page_size) - n_shared  # its own pages
+    if (args.kv_pages
+            and n_shared + pages_per_slot * max(batches) > args.kv_pages):
         sys.exit(f"error: {max(batches)} sequences of {last} positions need "
-                 f"{pages_per_slot * max(batches)} pages")
+                 f"{n_shared + pages_per_slot * max(batches)} pages")
 
     torch.manual_seed(1234)
     prompt = torch.randint(0, cfg.vocab_size, (args.prefill,)).tolist()
@@ -125,13 +148,15 @@ def main():
             for s in range(model.n_slots):
                 model.clear_slot(s)
             for s in slots:  # interleaved: no sequence is contiguous
-                model.set_slot_pages(s, [i * B + s
-                                         for i in range(pages_per_slot)])
+                model.set_slot_pages(
+                    s, list(range(n_shared))
+                    + [n_shared + i * B + s for i in range(pages_per_slot)])
         for s in slots:  # every sequence's prompt, one chunk per step
             for i in range(0, args.prefill, model.n_batches):
                 chunk = prompt[i: i + model.n_batches]
-                model.forward_rows(chunk, [s] * len(chunk),
-                                   list(range(i, i + len(chunk))))
+                model.forward_rows(
+                    chunk, [s] * len(chunk),
+                    list(range(shared + i, shared + i + len(chunk))))
         state = {"tokens": [7] * B, "pos": context}
         zeros, topps = [0.0] * B, [0.9] * B
 
@@ -147,8 +172,17 @@ def main():
         return entry(elapsed, B)
 
     rows = {}
+    if args.prefix_attn == "on":
+        model.set_prefix_attn(True, q80=True)
     for B in batches:
-        if args.stream_gemm != "ab":
+        if args.prefix_attn == "ab":
+            model.set_stream_gemm(args.stream_gemm == "on")
+            rows[str(B)] = {"off": [], "on": []}
+            for _ in range(3):
+                for name in ("off", "on"):
+                    model.set_prefix_attn(name == "on", q80=True)
+                    rows[str(B)][name].append(measure(B))
+        elif args.stream_gemm != "ab":
             model.set_stream_gemm(args.stream_gemm == "on")
             rows[str(B)] = measure(B)
         else:
@@ -197,6 +231,9 @@ def main():
                    "sampling": "on device, temperature 0",
                    "logprobs": args.logprobs,
                    "stream_gemm": args.stream_gemm,
+                   "shared_prefix": shared,
+                   "prefix_attn": args.prefix_attn,
+                   "gqa_attn": model.gqa_attn,
                    "data": "synthetic (random-init weights, random prompt)"},
     }))
 

@@ -193,6 +193,86 @@ def gqa_ab(kv_dtype="f16", page_size=0, positions=(512, 2048, 4096, 8192),
         f16 = None
 
 
+def prefix_ab(kv_dtype="f16", page_size=64, batches=(2, 8, 32),
+              prefixes=(256, 1024, 3584), suffixes=(64, 512), rounds=3,
+              pre_splits=(4, 8, 16, 32)):
+    """Decode-row attention of B sequences behind one shared prefix, alone in
+    an isolated hipGraph at the 8B shape (32 heads, kv_mul 4, hd 128, Q80
+    output, paged cache): every row has the same `prefix` leading tokens (the
+    same pool pages, one group) and `suffix` tokens of its own. k_attn_split
+    + combine (attn_paged) and k_attn_gqa + combine (attn_gqa_paged), which
+    read the prefix once per row, against the three launches of
+    attn_prefix_paged at every S_pre of pre_splits, all at the decode
+    schedule's S, interleaved over `rounds`: median (min..max) us per call.
+
+      python tools/kernel_bench.py prefix [--kv-dtype q80]"""
+    H0, hd, kvd, kv_mul, P = 32, 128, 1024, 4, page_size
+    q80 = kv_dtype == "q80"
+    print(f"\n-- shared-prefix decode attention, isolated graph, 8B shape, "
+          f"{kv_dtype} KV, pages of {P}, Q80 out "
+          "(us per call: median (min..max)) --")
+
+    def i32(x):
+        return torch.tensor(x, dtype=torch.int32, device=dev)
+
+    for B in batches:
+        for N in prefixes:
+            for sfx in suffixes:
+                pos, n_pre = N + sfx, N // P
+                own = sfx // P + 1
+                pages = n_pre + B * own
+                perm = torch.randperm(pages, generator=torch.Generator()
+                                      .manual_seed(pages)).tolist()
+                pt = i32([perm[:n_pre] + perm[n_pre + b * own:
+                                              n_pre + (b + 1) * own]
+                          for b in range(B)])
+                n = pages * P
+                if q80:
+                    planes = [torch.randint(-127, 128, (n, kvd), device=dev,
+                                            generator=g).to(torch.int8)
+                              for _ in range(2)]
+                    planes += [(a / 127 * (0.5 + torch.rand(
+                        n, kvd // 32, device=dev, generator=g))).half()
+                        for a in (0.3, 1.0)]
+                else:
+                    planes = [
+                        (torch.randn(n, kvd, device=dev, generator=g) * 0.3).half(),
+                        torch.randn(n, kvd, device=dev, generator=g).half()]
+                kw = dict(zip(("k_scales", "v_scales"), planes[2:]))
+                qv = torch.randn(B, H0 * hd, device=dev, generator=g)
+                y = torch.zeros(B, H0 * hd, device=dev)
+                z = [torch.zeros(B, H0 * hd, dtype=torch.int8, device=dev),
+                     torch.zeros(B, H0 * hd // 32, device=dev),
+                     torch.zeros(B, H0 * hd // 32, device=dev)]
+                rows = i32([[b * pt.shape[1], pos] for b in range(B)])
+                tables = (i32([[0, N]] * B), i32([[0, B]] + [[0, 0]] * 15),
+                          i32(list(range(B))), i32([1]))
+                S = 8 if pos < 512 else 16 if pos < 2048 else 32
+                ml = torch.zeros(B * H0 * S * 2, device=dev)
+                osc = torch.zeros(B * H0 * S * hd, device=dev)
+                head = (qv, H0 * hd, *planes[:2], y, rows, pt, P)
+                tail = (B, H0, kv_mul, hd, S, ml, osc)
+                cands = {
+                    "split": lambda: k.attn_paged(*head, *tail, *z, **kw),
+                    "gqa": lambda: k.attn_gqa_paged(*head, *tail, *z, **kw)}
+                for sp in pre_splits:
+                    pre = (torch.zeros(B * H0 * sp * 2, device=dev),
+                           torch.zeros(B * H0 * sp * hd, device=dev))
+                    cands[f"prefix S_pre={sp}"] = lambda sp=sp, pre=pre: \
+                        k.attn_prefix_paged(*head, *tables, *tail, sp, *pre,
+                                            *z, **kw)
+                t = {name: [] for name in cands}
+                for _ in range(rounds):
+                    for name, fn in cands.items():
+                        t[name].append(bench(fn, n=16, reps=3))
+                print(f"B={B:2d} prefix={N:4d} suffix={sfx:3d} S={S:2d}  "
+                      + "  ".join(
+                          f"{name}: {statistics.median(v):6.1f} "
+                          f"({min(v):.1f}..{max(v):.1f})"
+                          for name, v in t.items()), flush=True)
+                del planes
+
+
 def chunk_forms_ab(kv_dtype="f16", page_size=0, positions=(512, 2048, 4096, 8192),
                    batches=(32,), rounds=3):
     """The paged and Q80 forms of the chunk attention in an isolated hipGraph
@@ -480,6 +560,9 @@ def tile_ab(rounds=3, batches=(64, 96, 128)):
 
 if sys.argv[1:] == ["attn"]:
     attn_ab()
+    sys.exit(0)
+if sys.argv[1:2] == ["prefix"]:
+    prefix_ab("q80" if sys.argv[2:] == ["--kv-dtype", "q80"] else "f16")
     sys.exit(0)
 if sys.argv[1:2] in (["chunk"], ["chunk-rows"], ["gqa"]) and len(sys.argv) > 2:
     import argparse
